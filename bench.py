@@ -20,6 +20,16 @@ itself when ``--gpus N`` is given without WORLD_SIZE in the environment) the glo
 points range-partitioned by Delta/Omega; no collective touches the data path
 (weak scaling); a gloo barrier brackets the timed region and the max time over
 ranks is reported.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (headline fields,
+configuration and the roofline of the timed launches themselves).  ``--full`` adds every
+measurement that takes runs of its own: isolated launches (``kernel_ms_isolated``), the
+host-buffer boundary (``host_path``), ``end_to_end``, ``pipelined`` and the CPU baseline
+(``cpu_baseline``; ``--no-cpu-baseline`` leaves that one out of a full run).
+``--dump-outputs DIR`` writes what the last timed step left in HBM -- the arrays a caller
+of the timed path fetches -- as ``DIR/<name>.npy`` (float64, at most 64 MB: beyond that a
+fixed seeded sample of the points, their indices in ``points.npy``; summary rows that
+the evolution does not define are left out, ``summary_rows.npy`` names the rest).
 """
 from __future__ import annotations
 
@@ -76,6 +86,43 @@ def _measured_traffic(workload: str, method: str, n: int, kernel: str):
                 and r.get("kernel") == kernel):
             return r
     return None
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6    # --dump-outputs: all files of one rank together
+DUMP_SEED = 20260215
+DUMP_RESERVE = 8192               # the .npy headers and summary_rows
+
+
+def dump_outputs(dirname: str, rank: int, ws: int, n: int, arrays: dict) -> None:
+    """--dump-outputs: ``arrays`` maps a name to (array, point axis, entries per point along
+    that axis; point p owns p * g ... p * g + g - 1).  Everything goes out as float64
+    ``<name>.npy`` (``<name>.rank<r>.npy`` with more than one rank), with the point indices
+    in ``points``; if the full arrays exceed DUMP_MAX_BYTES, a sorted sample of the points
+    drawn from a fixed seed is written instead (the same points in every run).  A summary
+    row the kernel does not compute for this evolution (NaN at every point: the overlaps,
+    controlled phase and penalty of a Lindblad run) is left out, the rows written are
+    named in ``summary_rows``; any other non-finite value is an error."""
+    arrays = dict(arrays)
+    sfx = f".rank{rank}" if ws > 1 else ""
+    os.makedirs(dirname, exist_ok=True)
+    if "summary" in arrays:
+        a, axis, g = arrays["summary"]
+        rows = np.flatnonzero(~np.isnan(a).all(axis=1))
+        arrays["summary"] = (a[rows], axis, g)
+        np.save(os.path.join(dirname, f"summary_rows{sfx}.npy"), rows.astype(np.float64))
+    for name, (a, _, _) in arrays.items():
+        if not np.isfinite(a).all():
+            raise ValueError(f"--dump-outputs: {name} holds non-finite values")
+    per_point = 8 + sum(8 * (a.size // n) for a, _, _ in arrays.values())
+    keep = (DUMP_MAX_BYTES - DUMP_RESERVE) // per_point
+    pts = np.arange(n)
+    if n > keep:
+        pts = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))
+    for name, (a, axis, g) in arrays.items():
+        if n > keep:
+            a = np.take(a, (pts[:, None] * g + np.arange(g)).ravel(), axis=axis)
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+    np.save(os.path.join(dirname, f"points{sfx}.npy"), pts.astype(np.float64))
 
 
 def _dist():
@@ -294,6 +341,34 @@ def end_to_end_c4(args, eng, host_params, t_host_derive):
                      "derivation (physics.derive_batch) this replaces, one call")}
 
 
+def host_path_c(eng, params, protocol, n_steps, args, n):
+    """The host-buffer form of the boundary (ryd_run_batch: params H2D, kernel, state +
+    summary D2H) -- PCIe-inclusive, reported beside `value`, never as it."""
+    from noisyquantumsimulator_amd import engine as E
+    t_h = time.perf_counter()
+    rh = eng.run(params, protocol, "lindblad", n_steps=n_steps, method=args.method)
+    t_h = time.perf_counter() - t_h
+    assert np.all(rh.status == 0)
+    # warm calls (device workspace and pinned staging reused): the median of 5
+    hp = []
+    for _ in range(5):
+        t_h = time.perf_counter()
+        rh = eng.run(params, protocol, "lindblad", n_steps=n_steps, method=args.method)
+        t_h = time.perf_counter() - t_h
+        assert np.all(rh.status == 0)
+        hp.append((t_h, rh, eng.last_timeline()))
+    t_h, rh, tl = sorted(hp, key=lambda x: x[0])[len(hp) // 2]
+    bytes_d2h = 8 * (25 * 4 + E.N.NSUMMARY) * n + 4 * n
+    return {"points_per_s": n / t_h, "wall_ms": t_h * 1e3, "h2d_ms": rh.h2d_ms,
+            "kernel_ms": rh.kernel_ms, "d2h_ms": rh.d2h_ms, "bytes_d2h": bytes_d2h,
+            "d2h_gbs": bytes_d2h / (rh.d2h_ms * 1e-3) / 1e9 if rh.d2h_ms > 0 else None,
+            "host_pack_ms": tl["pack_ms"], "host_unpack_ms": tl["unpack_ms"],
+            "host_pack_gbs": 8 * 38 * n / (tl["pack_ms"] * 1e-3) / 1e9,
+            "host_unpack_gbs": bytes_d2h / (tl["unpack_ms"] * 1e-3) / 1e9, "calls": "median of 5 warm calls",
+            "staging": "persistent device workspace + pinned staging per handle slot; "
+                       "unpack into the caller's strided numpy arrays on host threads"}
+
+
 def end_to_end_c2():
     """simulate_CZ_gate_batch on the C2 grid: derivation (host) + engine (host-buffer
     boundary) + the reference-penalty epilogue (zheevr on host threads, the batch call's
@@ -455,7 +530,7 @@ def run_c1(args, ws, rank, local, pg):
                                                "reference's default noisy LP point (14 c_ops collapsed to 8 channels); "
                                                "breakdown from simulate_CZ_gate_batch(n=1) timings"),
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(10, 1, "c1")
         out["cpu_over_gpu"] = out["cpu_baseline"]["value"] / out["value"]
     print(json.dumps(out), flush=True)
@@ -501,10 +576,15 @@ def run_c5(args, ws, rank, local, pg):
     # the dominant kernel's average launch duration: HIP events on its stream over the
     # timed region (back-to-back launches; the only work on that stream)
     k_ms = db.mark_elapsed() / args.steps
-    # one launch at a time, events around each (includes event/sync overhead)
-    k_iso = float(np.mean([db.launch(timed=True) for _ in range(max(3, min(args.steps, 10)))]))
     res = db.fetch()
     assert np.all(res.status == 0), "engine reported per-point failures"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, ws, n,
+                     {"rho_re": (res.rho.real, 0, 1), "rho_im": (res.rho.imag, 0, 1), "se": (res.se, 0, 1),
+                      "summary": (res.summary, 1, 1), "status": (res.status, 0, 1)})
+    # --full: one launch at a time, events around each (includes event/sync overhead)
+    k_iso = (float(np.mean([db.launch(timed=True) for _ in range(max(3, min(args.steps, 10)))]))
+             if args.full else None)
     it_use = float(res.col("ITER_USEFUL").sum())
     it_exec = float(res.col("ITER_EXEC").sum())
     napply = float(res.col("RESERVED").sum())
@@ -553,7 +633,7 @@ def run_c5(args, ws, rank, local, pg):
                          "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic,
                          "bytes_per_launch": C5_BYTES_PER_POINT * n},
     }
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline:
+    if rank == 0 and ws == 1 and args.full and not args.no_cpu_baseline:
         procs = cpu_procs()
         out["cpu_baseline"] = cpu_baseline(min(args.cpu_sample, 64), procs, "c5")
     if rank == 0:
@@ -723,6 +803,8 @@ def run_aux(args, ws, rank, local, pg):
     if args.workload == "coherence":
         coh, st = db.fetch()
         assert np.all(st == 0), "engine reported per-point failures"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rank, ws, n, {"coherences": (coh, 1, 1), "status": (st, 0, 1)})
         if os.environ.get("RYD_COH_PROP", "1") != "0":
             kernel = "coherence_prop_kernel"
             flops = coh_prop_flops(params, protocol)
@@ -738,6 +820,9 @@ def run_aux(args, ws, rank, local, pg):
     else:
         res = db.fetch()
         assert np.all(res.status == 0), "engine reported per-point failures"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rank, ws, n, {"state": (res.state, 1, 4), "summary": (res.summary, 1, 1),
+                                                          "status": (res.status, 0, 1)})
         if args.workload == "ket":
             flops = (res.matvec_useful * FLOP_PER_KET_BLOCK_SEG
                      + float(res.col("NSQUARE").sum()) * FLOP_PER_KET_BLOCK_BUILD)
@@ -853,7 +938,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (isolated launches, host-buffer path, "
+                         "end to end, pipelined, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample", type=int, default=1024)
     ap.add_argument("--method", default="chebyshev",
                     choices=["chebyshev", "cheb_squaring", "cheb_vector"])
@@ -875,6 +965,8 @@ def main():
                     help="C5 ladder levels (0: exact jump times; -1: trajectories.DEFAULT_LADDER)")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)   # launcher test: no GPU
     args = ap.parse_args()
+    if args.dump_outputs and args.workload in ("c1", *OPT_PUBLISHED):
+        ap.error(f"--dump-outputs: the {args.workload} line times whole calls, not a resident batch")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no torchrun around us: start the N ranks ourselves (before any GPU call)
@@ -940,10 +1032,14 @@ def main():
     # timed region (back-to-back launches; the only work on that stream)
     k_ms = db.mark_elapsed() / args.steps
 
-    # one launch at a time, events around each (includes event/sync overhead)
-    k_iso = float(np.mean([db.launch(timed=True) for _ in range(max(3, min(args.steps, 10)))]))
     res = db.fetch()
     assert np.all(res.status == 0), "engine reported per-point failures"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, ws, n, {"state": (res.state, 1, 4), "summary": (res.summary, 1, 1),
+                                                      "status": (res.status, 0, 1)})
+    # --full: one launch at a time, events around each (includes event/sync overhead)
+    k_iso = (float(np.mean([db.launch(timed=True) for _ in range(max(3, min(args.steps, 10)))]))
+             if args.full else None)
     # algorithmic bytes per launch: 15 param columns read, 25x4 state + 19 summary doubles
     # + 1 status word written per point
     bytes_per_point = 8 * 15 + 8 * 100 + 8 * 19 + 4
@@ -975,35 +1071,13 @@ def main():
     tr = _measured_traffic(args.workload, args.method, n, dom_kernel)
     traffic = tr["bytes_per_launch"] if tr else None
 
-    # the host-buffer form of the boundary (ryd_run_batch: params H2D, kernel, state +
-    # summary D2H) -- PCIe-inclusive, reported beside `value`, never as it
-    t_h = time.perf_counter()
-    rh = eng.run(params, protocol, "lindblad", n_steps=n_steps, method=args.method)
-    t_h = time.perf_counter() - t_h
-    assert np.all(rh.status == 0)
-    # warm calls (device workspace and pinned staging reused): the median of 5
-    hp = []
-    for _ in range(5):
-        t_h = time.perf_counter()
-        rh = eng.run(params, protocol, "lindblad", n_steps=n_steps, method=args.method)
-        t_h = time.perf_counter() - t_h
-        assert np.all(rh.status == 0)
-        hp.append((t_h, rh, eng.last_timeline()))
-    t_h, rh, tl = sorted(hp, key=lambda x: x[0])[len(hp) // 2]
-    bytes_d2h = 8 * (25 * 4 + E.N.NSUMMARY) * n + 4 * n
-    host_path = {"points_per_s": n / t_h, "wall_ms": t_h * 1e3, "h2d_ms": rh.h2d_ms,
-                 "kernel_ms": rh.kernel_ms, "d2h_ms": rh.d2h_ms, "bytes_d2h": bytes_d2h,
-                 "d2h_gbs": bytes_d2h / (rh.d2h_ms * 1e-3) / 1e9 if rh.d2h_ms > 0 else None,
-                 "host_pack_ms": tl["pack_ms"], "host_unpack_ms": tl["unpack_ms"],
-                 "host_pack_gbs": 8 * 38 * n / (tl["pack_ms"] * 1e-3) / 1e9,
-                 "host_unpack_gbs": bytes_d2h / (tl["unpack_ms"] * 1e-3) / 1e9, "calls": "median of 5 warm calls",
-                 "staging": "persistent device workspace + pinned staging per handle slot; "
-                            "unpack into the caller's strided numpy arrays on host threads"}
-    out_e2e = pipelined = None
-    if args.workload == "c2" and ws == 1:
+    host_path = out_e2e = pipelined = None
+    if args.full:
+        host_path = host_path_c(eng, params, protocol, n_steps, args, n)
+    if args.full and args.workload == "c2" and ws == 1:
         out_e2e = end_to_end_c2()
         pipelined = pipelined_c2(params, protocol, n_steps, args, dev, n)
-    if args.workload == "c4":
+    if args.full and args.workload == "c4":
         out_e2e = end_to_end_c4(args, eng, params, t_host_derive)
     strong = args.workload == "c4"
     proxy = strong and args.c4_shards > 0
@@ -1038,7 +1112,7 @@ def main():
                          "unit": "GB/s", "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic,
                          "bytes_per_launch": bytes_per_point * n},
     }
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline:
+    if rank == 0 and ws == 1 and args.full and not args.no_cpu_baseline:
         procs = cpu_procs()
         # C3 points cost ~6 core-seconds each on the CPU path: a smaller sample
         sample = args.cpu_sample if args.workload != "c3" else min(args.cpu_sample, 32)
