@@ -51,7 +51,8 @@ T = dict(DIM=27, RHO_WIDTH=1458, SE_WIDTH=729, EXACT=0, LADDER_MAX=40, REC_WIDTH
 TS = dict(MEAN_JUMPS=0, FRAC_JUMPED=1, MAX_JUMPS=2, TRACE=3, QUBIT_POP=4, ITER_USEFUL=5,
           ITER_EXEC=6, NLADDER=7, NSQUARE=8, RESERVED=9)
 T_NSUMMARY = 10
-# exact-mode kernel selection (ryd_traj_desc.flags)
+# ryd_traj_desc.flags: "auto" and "lanes" name the one exact-mode kernel; "rows" is the
+# header's name for the reserved bit 0 of a retired kernel, which the library refuses
 T_FLAG = {"auto": 0, "rows": 1, "lanes": 2}
 
 # ryd_last_timeline layout

@@ -470,7 +470,6 @@ struct TrajArgs {
   double* stats;
   uint32_t* arrive;
   uint64_t seed;
-  int rows;                    // exact mode: 1 traj3r (16-lane rows), 0 traj3e
   double psi0[T_NV];
 };
 
@@ -842,31 +841,10 @@ __global__ __launch_bounds__(T_WAVE, T_WAVES_PER_SIMD) void traj3_kernel(TrajArg
 
 #include "ryd_traj_sym.inc"
 #include "ryd_traj_eig.inc"
-#include "ryd_traj_wg.inc"
-#include "ryd_traj_rows.inc"
-
-// RYD_T_WG=1 selects traj3w_kernel (a workgroup per point) for exact mode; the default is
-// traj3e_kernel (a trajectory per lane, trajectory ranges split over waves for small launches)
-bool t_wg_enabled() {
-  const char* e = getenv("RYD_T_WG");
-  return e && e[0] == '1';
-}
-
-// exact-mode kernel: the descriptor's flag, else RYD_T_ROWS (0: traj3e, 1: rows), else traj3e
-bool t_rows_selected(uint32_t flags) {
-  if (flags & RYD_T_FLAG_ROWS) return true;
-  if (flags & RYD_T_FLAG_LANES) return false;
-  const char* e = getenv("RYD_T_ROWS");
-  if (e && e[0]) return e[0] != '0';
-  return false;                                  // traj3e: 2.7x faster on C5 (DESIGN.md §9)
-}
 
 template <int PROTO>
 int t_launch_proto(const TrajArgs& ta, hipStream_t stream) {
-  if (ta.L == RYD_T_EXACT) {
-    if (t_wg_enabled()) return tw_launch_proto<PROTO>(ta, stream);
-    return ta.rows ? tr_launch_proto<PROTO>(ta, stream) : te_launch_proto<PROTO>(ta, stream);
-  }
+  if (ta.L == RYD_T_EXACT) return te_launch_proto<PROTO>(ta, stream);
   if (t_sym_enabled()) return ts_launch_proto<PROTO>(ta, stream);
   const size_t lds = t_lds_bytes(ta.L);
   if (lds > 32768)
@@ -891,9 +869,8 @@ int validate_traj(const ryd_traj_desc* d, int64_t n, int64_t ldp) {
     return fail(RYD_ERR_INVALID, "BANGBANG needs 1 <= n_steps (max segments) <= 8");
   if (d->n_traj < T_WAVE || d->n_traj % T_WAVE != 0 || d->n_traj > (1 << 20))
     return fail(RYD_ERR_INVALID, "n_traj must be a positive multiple of 64 (<= 2^20)");
-  if ((d->flags & ~(RYD_T_FLAG_ROWS | RYD_T_FLAG_LANES)) != 0u ||
-      (d->flags & RYD_T_FLAG_ROWS && d->flags & RYD_T_FLAG_LANES))
-    return fail(RYD_ERR_INVALID, "flags: at most one of RYD_T_FLAG_ROWS / RYD_T_FLAG_LANES");
+  if ((d->flags & ~RYD_T_FLAG_LANES) != 0u)
+    return fail(RYD_ERR_INVALID, "flags: RYD_T_FLAG_ROWS (1) was retired; use 0 or RYD_T_FLAG_LANES");
   if (d->ladder_levels < RYD_T_EXACT || d->ladder_levels > RYD_T_LADDER_MAX)
     return fail(RYD_ERR_INVALID, "ladder_levels must be RYD_T_EXACT (0) or in [1, RYD_T_LADDER_MAX]");
   if (d->ladder_levels == RYD_T_EXACT && d->protocol == RYD_PROTO_LP_SHAPED && d->shape != RYD_SHAPE_SQUARE)
@@ -940,7 +917,6 @@ int launch_traj(const ryd_traj_desc* d, const double* dp, int64_t n, int64_t ldp
   ta.stats = nullptr;
   ta.arrive = nullptr;
   ta.seed = d->seed;
-  ta.rows = t_rows_selected(d->flags) ? 1 : 0;
   for (int e = 0; e < T_NV; ++e) ta.psi0[e] = d->psi0[e];
   switch (d->protocol) {
     case RYD_PROTO_LP_SQUARE: return t_launch_proto<RYD_PROTO_LP_SQUARE>(ta, stream);

@@ -1241,8 +1241,8 @@ int te_launch_proto(const TrajArgs& ta, hipStream_t stream) {
   arg.npair = (ta.n + TE_P - 1) / TE_P;
   arg.split = te_split(ta.n, ta.n_traj);
   // split launches run cooperatively (one workgroup per wave pair, its ranges as its waves,
-  // at most TE_COOP_MAX) unless RYD_TE_COOP=0 keeps the last-wave merge (the A/B; the rows
-  // are the same either way)
+  // at most TE_COOP_MAX) unless RYD_TE_COOP=0 keeps the last-wave merge (the A/B; the
+  // outputs are the same bits either way)
   const char* ce = getenv("RYD_TE_COOP");
   const bool coop_on = !(ce && ce[0] == '0');
   if (coop_on) arg.split = std::min(arg.split, TE_COOP_MAX);

@@ -424,7 +424,7 @@ traj3s_kernel(TrajArgs a) {
   const int64_t i = blockIdx.x;
   const int lane = threadIdx.x;
   if (i >= a.n) return;
-  // the fallback pass after traj3w_kernel: only the points it declined
+  // the fallback pass after traj3e_kernel: only the points it declined
   if (a.fix && !(a.status[i] & RYD_STATUS_EXACT_FALLBACK)) return;
   const uint32_t st0 = a.fix ? RYD_STATUS_EXACT_FALLBACK : 0u;
   const uint64_t gpoint = (uint64_t)(a.point_offset + a.point_stride * i);

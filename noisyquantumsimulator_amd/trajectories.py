@@ -92,11 +92,12 @@ def _psi_array(psi0: np.ndarray) -> np.ndarray:
 def make_traj_desc(protocol: str, psi0: np.ndarray, n_traj: int = 256, seed: int = 0,
                    ladder_levels: Optional[int] = DEFAULT_LADDER, n_steps: int = 0,
                    shape: str = "square", kernel: str = "auto") -> N.TrajDesc:
-    """``kernel`` picks the exact-mode kernel (include/ryd_engine.h RYD_T_FLAG_*): "rows"
-    (one trajectory per 16-lane DPP row, pass 1 once per point), "lanes" (one trajectory per
-    lane, traj3e), or "auto" (the library's default, lanes; env RYD_T_ROWS=1 -> rows)."""
-    if kernel not in N.T_FLAG:
-        raise ValueError(f"kernel must be one of {sorted(N.T_FLAG)}")
+    """``kernel`` sets the descriptor's flags (include/ryd_engine.h): "auto" (0) or "lanes"
+    (RYD_T_FLAG_LANES).  Exact mode has one kernel (traj3e, one trajectory per lane), so the
+    two mean the same; any other name, the retired "rows" included, is a ValueError."""
+    # the library's own rule (validate_traj): every bit but RYD_T_FLAG_LANES is refused
+    if N.T_FLAG.get(kernel, ~0) & ~N.T_FLAG["lanes"]:
+        raise ValueError('kernel must be "auto" or "lanes" (the "rows" kernel was retired)')
     d = N.TrajDesc()
     d.flags = N.T_FLAG[kernel]
     d.abi_version = N.RYD_ABI_VERSION
@@ -163,7 +164,8 @@ def run_trajectories(engine: Engine, params: np.ndarray, protocol: str, psi0: Op
                      n_steps: Optional[int] = None, shape: str = "square",
                      records: bool = False, kernel: str = "auto") -> TrajectoryResult:
     """Host-buffer form: every point of ``params`` (``pack_params`` columns; atom-A
-    rates are used for all three atoms) through ``n_traj`` trajectories."""
+    rates are used for all three atoms) through ``n_traj`` trajectories.  ``kernel``: "auto"
+    or "lanes", the same exact-mode kernel (``make_traj_desc``)."""
     params = np.ascontiguousarray(params, dtype=np.float64)
     if params.shape[0] != N.NPARAM:
         raise ValueError(f"params must have shape ({N.NPARAM}, n)")
@@ -191,7 +193,8 @@ class TrajectoryDeviceBatch:
     """Inputs resident in HBM on one device slot, for timed re-runs (bench.py) and
     shards launched with their global point indices: point i of the batch is global point
     ``point_offset + point_stride * i`` (a range shard: stride 1; rank r of a strided split
-    over N ranks: offset r, stride N), which keys its trajectories' random streams."""
+    over N ranks: offset r, stride N), which keys its trajectories' random streams.
+    ``kernel`` as in ``make_traj_desc``: "auto" or "lanes", one kernel either way."""
 
     def __init__(self, engine: Engine, params: np.ndarray, protocol: str, psi0: Optional[np.ndarray] = None,
                  n_traj: int = 256, seed: int = 0, ladder_levels: Optional[int] = DEFAULT_LADDER,

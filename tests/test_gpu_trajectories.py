@@ -8,6 +8,7 @@ C-ABI (ryd_run_trajectories), against the CPU oracle (oracle/three_atom_oracle.p
   quantum, same final ket as the exact-jump-time oracle on the same Philox stream;
 * launch-shape independence (bit-exact), bad inputs, full 4096-point C5 grid properties.
 """
+import ctypes
 import warnings
 
 import numpy as np
@@ -47,10 +48,10 @@ def _two_atom(si, n=2):
 
 
 LADDERS = [16, N.T["EXACT"]]          # the ladder walk and the exact-jump-time kernel
-# (ladder_levels, exact-mode kernel): the ladder, traj3e (one trajectory per lane, the
-# default) and traj3r (one trajectory per 16-lane DPP row, include/ryd_engine.h RYD_T_FLAG_ROWS)
-MODES = [(16, "auto"), (N.T["EXACT"], "lanes"), (N.T["EXACT"], "rows")]
-EXACT_KERNELS = ["lanes", "rows"]
+# (ladder_levels, kernel): the ladder, and traj3e (one trajectory per lane), the one exact
+# kernel, named by its flag (include/ryd_engine.h RYD_T_FLAG_LANES)
+MODES = [(16, "auto"), (N.T["EXACT"], "lanes")]
+EXACT_KERNELS = ["lanes"]
 
 
 @pytest.mark.parametrize("ladder", LADDERS)
@@ -282,6 +283,32 @@ def test_bad_inputs(eng, ladder):
         TR.run_trajectories(eng, _two_atom(lambda excitation: CF.LPSimulationInputs(
             excitation=excitation, pulse_shape="cosine")), "lp_shaped", n_traj=256, n_steps=40, shape="cosine",
             ladder_levels=N.T["EXACT"])
+    # the retired kernel's selectors are refused before any launch: bit 0 of the
+    # descriptor's flags by the library, its name by the package
+    desc = TR.make_traj_desc("lp_square", TR.plus_state(), n_traj=256, ladder_levels=ladder,
+                             n_steps=E.default_n_steps("lp_square", p))
+    desc.flags = 1
+    n = p.shape[1]
+    out = [np.zeros((n, N.T["RHO_WIDTH"])), np.zeros((n, N.T["SE_WIDTH"])), np.zeros((N.T_NSUMMARY, n))]
+    status = np.zeros(n, dtype=np.uint32)
+    dptr = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    with pytest.raises(N.EngineError, match="RYD_T_FLAG_ROWS"):
+        N.check(eng.lib.ryd_run_trajectories(
+            eng.handle, ctypes.byref(desc), dptr(p), n, n, dptr(out[0]), dptr(out[1]), dptr(out[2]), n, None,
+            status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), None))
+    assert not any(a.any() for a in out) and not status.any()
+    with pytest.raises(ValueError):
+        TR.run_trajectories(eng, p, "lp_square", n_traj=256, ladder_levels=ladder, kernel="rows")
+
+
+def test_auto_is_lanes(eng):
+    """Exact mode has one kernel: the library's default and RYD_T_FLAG_LANES give the same
+    bits (no selector besides the descriptor is left)."""
+    p = _c5(list(range(0, 4096, 512)), scale=20.0)
+    kw = dict(n_traj=256, seed=5, ladder_levels=N.T["EXACT"], records=True)
+    a = TR.run_trajectories(eng, p, "lp_square", kernel="auto", **kw)
+    b = TR.run_trajectories(eng, p, "lp_square", kernel="lanes", **kw)
+    assert np.array_equal(a.rho, b.rho) and np.array_equal(a.se, b.se) and np.array_equal(a.records, b.records)
 
 
 @pytest.mark.parametrize("ladder,kernel", MODES)
@@ -328,20 +355,3 @@ def test_c5_full_grid_properties(eng, ladder, kernel):
         np.testing.assert_array_equal(o.rho, r.rho[rank::8])
         np.testing.assert_array_equal(o.se, r.se[rank::8])
         np.testing.assert_array_equal(o.summary[det], r.summary[det][:, rank::8])
-
-
-def test_exact_kernels_agree(eng):
-    """traj3r and traj3e walk the same Philox streams to the same jump times; they differ
-    only in the order of the floating-point sums (one row per trajectory vs one lane), so the
-    outputs agree to rounding and the jump records exactly in count and channel."""
-    warnings.simplefilter("ignore")
-    p = E.pack_params(SW.blockade_grid_3atom())[:, ::8].copy()
-    kw = dict(n_traj=256, seed=20260215, ladder_levels=N.T["EXACT"], records=True)
-    a = TR.run_trajectories(eng, p, "lp_square", kernel="lanes", **kw)
-    b = TR.run_trajectories(eng, p, "lp_square", kernel="rows", **kw)
-    assert np.all(a.status == 0) and np.all(b.status == 0)
-    np.testing.assert_allclose(b.rho, a.rho, atol=1e-12, rtol=0)
-    np.testing.assert_allclose(b.se, a.se, atol=1e-12, rtol=0)
-    np.testing.assert_array_equal(b.n_jumps(), a.n_jumps())
-    np.testing.assert_array_equal(b.jump_channels(), a.jump_channels())
-    np.testing.assert_allclose(b.jump_times(), a.jump_times(), atol=1e-12 * float(p[N.P["TAU"]].max()), rtol=0)

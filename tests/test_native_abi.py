@@ -76,3 +76,14 @@ def test_evolve_generic_validates_before_any_gpu_call():
     """ryd_evolve_generic rejects a NULL handle and bad sizes without touching a device."""
     lib = N.load()
     assert lib.ryd_evolve_generic(None, 9, 1, 0, 1, 1, None, None, None, None, None, None) == -1   # RYD_ERR_INVALID
+
+
+def test_retired_rows_kernel_has_no_selector():
+    """Bit 0 of ryd_traj_desc.flags only keeps its name: the names that select a kernel are
+    "auto" and "lanes", and the package refuses "rows" before it builds a descriptor."""
+    from noisyquantumsimulator_amd import trajectories as TR
+    assert {k for k, v in N.T_FLAG.items() if not v & ~N.T_FLAG["lanes"]} == {"auto", "lanes"}
+    for kernel in ("rows", "wg"):
+        with pytest.raises(ValueError):
+            TR.make_traj_desc("lp_square", TR.plus_state(), kernel=kernel)
+    assert TR.make_traj_desc("lp_square", TR.plus_state(), kernel="lanes").flags == N.T_FLAG["lanes"]

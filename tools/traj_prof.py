@@ -3,7 +3,6 @@
 Usage on the GPU box:
     RYD_ENGINE_LIB=$PWD/build/libryd_tprof.so python tools/traj_prof.py [ladder]
 """
-import os
 import sys
 import warnings
 
@@ -34,14 +33,6 @@ for nm, c in zip(names, cols):
     v = r.col(c)
     print(f"  {nm:15s} mean {v.mean():10.0f}  ({100 * v.mean() / tot.mean():5.1f} %)  p90 {np.percentile(v, 90):10.0f}")
 print(f"  {'total':15s} mean {tot.mean():10.0f}  max {tot.max():10.0f}")
-if L == 0 and os.environ.get("RYD_T_WG", "0") == "1":      # traj3w_kernel: the eigen-decomposition's share of pass 1
-    v = r.col("NLADDER")
-    print(f"  (of pass 1: eigen-decomposition mean {v.mean():10.0f}  p90 {np.percentile(v, 90):10.0f})")
-    trips, ev, jf = r.col("ITER_USEFUL"), r.col("NSQUARE"), r.col("ITER_EXEC")
-    print(f"  wave 0 walk: trips mean {trips.mean():.1f} max {trips.max():.0f}; cycles per trip "
-          f"{(ev.sum() + jf.sum()) / trips.sum():.0f} (restart + evaluation {ev.sum() / trips.sum():.0f}, "
-          f"segments/jumps/ends/fetch {jf.sum() / trips.sum():.0f})")
-    sys.exit(0)
 if L == 0:                       # traj3e_kernel: the outputs phase's split (range merges)
     arr, mrg = r.col("ITER_USEFUL"), r.col("ITER_EXEC")
     print(f"  (of outputs: the merge's jumper lists mean {arr.mean():.0f} p90 {np.percentile(arr, 90):.0f}; "
