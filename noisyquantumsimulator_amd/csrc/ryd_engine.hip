@@ -92,34 +92,43 @@ __device__ __forceinline__ double col(const double* p, int f, int64_t ld, int64_
   return p[(int64_t)f * ld + i];
 }
 
-template <int PROTO>
-__device__ __forceinline__ PointP load_point(const double* __restrict__ p, int64_t ld, int64_t i) {
+// The point's columns through an accessor get(f) = column f of this point (load_point: the
+// plain per-lane index; ryd_sym16.inc: a wave-uniform base plus a 32-bit lane offset).
+template <int PROTO, typename Get>
+__device__ __forceinline__ PointP load_point_with(Get get) {
   PointP q;
-  q.prm = p; q.ld = ld; q.i = i;
-  q.Om = col(p, RYD_P_OMEGA, ld, i);
-  q.Dl = col(p, RYD_P_DELTA, ld, i);
-  q.V = col(p, RYD_P_V, ld, i);
-  q.d1 = col(p, RYD_P_DELTA1, ld, i);
+  q.prm = nullptr; q.ld = 0; q.i = 0;
+  q.Om = get(RYD_P_OMEGA);
+  q.Dl = get(RYD_P_DELTA);
+  q.V = get(RYD_P_V);
+  q.d1 = get(RYD_P_DELTA1);
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    q.gA[c] = col(p, RYD_P_G1_A + c, ld, i);
-    q.gB[c] = col(p, RYD_P_G1_B + c, ld, i);
+    q.gA[c] = get(RYD_P_G1_A + c);
+    q.gB[c] = get(RYD_P_G1_B + c);
   }
-  q.tau = col(p, RYD_P_TAU, ld, i);
+  q.tau = get(RYD_P_TAU);
   q.xr = q.xi = q.corr = q.A = q.wmod = q.phoff = q.otau = 0.0;
   q.nseg = 0;
   if (PROTO == RYD_PROTO_LP_SQUARE || PROTO == RYD_PROTO_LP_SHAPED) {
-    q.xr = col(p, RYD_P_XI_RE, ld, i);
-    q.xi = col(p, RYD_P_XI_IM, ld, i);
-    q.corr = (PROTO == RYD_PROTO_LP_SHAPED) ? col(p, RYD_P_AREA_CORR, ld, i) : 1.0;
+    q.xr = get(RYD_P_XI_RE);
+    q.xi = get(RYD_P_XI_IM);
+    q.corr = (PROTO == RYD_PROTO_LP_SHAPED) ? get(RYD_P_AREA_CORR) : 1.0;
   } else if (PROTO == RYD_PROTO_SMOOTH_JP) {
-    q.A = col(p, RYD_P_A, ld, i);
-    q.wmod = col(p, RYD_P_OMEGA_MOD, ld, i);
-    q.phoff = col(p, RYD_P_PHI_OFF, ld, i);
+    q.A = get(RYD_P_A);
+    q.wmod = get(RYD_P_OMEGA_MOD);
+    q.phoff = get(RYD_P_PHI_OFF);
   } else {
-    q.otau = col(p, RYD_P_OMEGA_TAU, ld, i);
-    q.nseg = (int)col(p, RYD_P_NSEG, ld, i);
+    q.otau = get(RYD_P_OMEGA_TAU);
+    q.nseg = (int)get(RYD_P_NSEG);
   }
+  return q;
+}
+
+template <int PROTO>
+__device__ __forceinline__ PointP load_point(const double* __restrict__ p, int64_t ld, int64_t i) {
+  PointP q = load_point_with<PROTO>([&](int f) { return col(p, f, ld, i); });
+  q.prm = p; q.ld = ld; q.i = i;
   return q;
 }
 

@@ -237,15 +237,18 @@ __device__ __forceinline__ void seg_polar(const PointP& q, int s, int n_steps, b
       a = q.Om;
       c = 1.0;
       sn = 0.0;
-    } else if (frame_ok) {                       // |xi| = 1 (compute_phase_shift_xi)
-      a = q.Om;
+    } else {
+      a = q.Om;                                  // |xi| = 1 (compute_phase_shift_xi)
       c = q.xr;
       sn = q.xi;
-    } else {                                     // ABI callers may pass any xi
-      const double m = sqrt(q.xr * q.xr + q.xi * q.xi);
-      a = q.Om * m;
-      c = m > 0.0 ? q.xr / m : 1.0;
-      sn = m > 0.0 ? q.xi / m : 0.0;
+      // ABI callers may pass any xi: the normalisation (a sqrt and two divisions) sits
+      // behind a wave-uniform branch, so a wave of unit xi never issues it
+      if (__builtin_amdgcn_ballot_w64(!frame_ok) != 0 && !frame_ok) {
+        const double m = sqrt(q.xr * q.xr + q.xi * q.xi);
+        a = q.Om * m;
+        c = m > 0.0 ? q.xr / m : 1.0;
+        sn = m > 0.0 ? q.xi / m : 0.0;
+      }
     }
   } else if (PROTO == RYD_PROTO_SMOOTH_JP) {     // simulation.py:1698-1731
     a = q.Om;
@@ -440,7 +443,6 @@ __device__ __forceinline__ void cheb_unit16(double (&out)[NS], int r, double x, 
     return;
   }
   const int kcut = (kmax + 1) & ~1;
-  const double i2x = active ? 2.0 / x : 0.0;
   double bA[NS], bB[NS];
 #pragma unroll
   for (int e = 0; e < NS; ++e) bA[e] = bB[e] = 0.0;
@@ -454,6 +456,7 @@ __device__ __forceinline__ void cheb_unit16(double (&out)[NS], int r, double x, 
     if constexpr (RYD_MASKED_ADD == 3) add_unit15_dpp(b, a, sel);
     else add_unit15<0>(b, a);
   };
+  const double i2x = active ? 2.0 / x : 0.0;
   // J_KS = seed, J_KS+1 = 0; then J_KS-1 and the Miller-only pairs above the cut
   double Jp2 = 0.0, Jp1 = active ? MILLER_SEED : 0.0;
   double S = 2.0 * Jp1;
@@ -471,7 +474,22 @@ __device__ __forceinline__ void cheb_unit16(double (&out)[NS], int r, double x, 
     Jp2 = Jp1;
     Jp1 = Jk1;
   }
-  for (int k = kcut; k >= 2; k -= 2) {
+  // The first pair (k = kcut >= 2) is peeled: bA is still zero there, so its first
+  // application adds exact zeros to bB = c_k e_r and is left out (same bits).
+  {
+    const int k = kcut;
+    const double Jk = fma(i2x * (double)(k + 1), Jp1, -Jp2);
+    Jp2 = Jp1;
+    Jp1 = Jk;
+    S = fma(2.0, Jk, S);
+    unit_add(bB, k <= kt ? 2.0 * Jk : 0.0);
+    const double Jk1 = fma(i2x * (double)k, Jp1, -Jp2);
+    Jp2 = Jp1;
+    Jp1 = Jk1;
+    unit_add(bA, k - 1 <= kt ? 2.0 * Jk1 : 0.0);
+    apply2Y(bB, bA);
+  }
+  for (int k = kcut - 2; k >= 2; k -= 2) {
     double Jk = fma(i2x * (double)(k + 1), Jp1, -Jp2);
     Jp2 = Jp1;
     Jp1 = Jk;
@@ -529,15 +547,6 @@ constexpr int SEG_M = 10, SEG_Q = 11, SEG_P = 14;
 __host__ __device__ constexpr int seg_old(int n) {      // plain segment coordinate -> triangle index
   return n == 0 ? 0 : n == 1 ? 1 : n == 2 ? 3 : n == 3 ? 4 : n == 4 ? 2 : n == 5 ? 5 : n == 6 ? 7
        : n == 7 ? 8 : n == 8 ? 10 : n == 9 ? 11 : n == 12 ? 6 : n == 13 ? 9 : 0;
-}
-// Row sources of the segment-order propagator (see "the segment phase" below): lane r's
-// row of S U is a1 * triangle row seg_row1(r) + a2 * triangle row seg_row2(r).  4-bit
-// nibble tables (lane 15: row 0, weight 0).
-__device__ __forceinline__ int seg_row1(int r) {    // 0 1 3 4 2 5 7 8 10 11 12 13 6 9 12 0
-  return (int)((0xc96dcba87524310ull >> (4 * r)) & 15);
-}
-__device__ __forceinline__ int seg_row2(int r) {    // as seg_row1 with m, p -> (4,4)
-  return (int)((0xe96deba87524310ull >> (4 * r)) & 15);
 }
 
 // Build this point's phase-0 propagator for (amplitude a, detuning dl, duration dt)
@@ -623,18 +632,26 @@ __device__ __forceinline__ void build16(double (&u)[NS], double (&Ut)[S16_PPW][N
   // ---- (3) transpose through LDS: lane r takes row r of U' = S U S^-1 (segment order)
   wave_sync();
   if (lane_ok) {
-#pragma unroll
-    for (int k = 0; k < NS; ++k) Ut[p][k][r] = v[k];
+    // the row side of S on the column-held values (m = t33 - t44, q = 2 t34, p = t33 + t44:
+    // 3 ops per lane), written in segment order: Ut[p][n][c] = (S U)[n][c]
+    static_for<NS>([&](auto N) {
+      constexpr int nn = decltype(N)::value;
+      double w;
+      if constexpr (nn == SEG_M) w = v[sym_index(3, 3)] - v[sym_index(4, 4)];
+      else if constexpr (nn == SEG_Q) w = 2.0 * v[sym_index(3, 4)];
+      else if constexpr (nn == SEG_P) w = v[sym_index(3, 3)] + v[sym_index(4, 4)];
+      else w = v[seg_old(nn)];
+      Ut[p][nn][r] = w;
+    });
   }
   wave_sync();
-  // row r of S U: a1 * (triangle row r1) + a2 * (triangle row r2); an inactive point's
-  // columns are the unit vectors, U = I, and so is U' (the 1/2 weights are exact)
-  const int r1 = seg_row1(r), r2 = seg_row2(r);
-  const double a1 = r == 11 ? 2.0 : (r == 15 ? 0.0 : 1.0);
-  const double a2 = r == 10 ? -1.0 : (r == 14 ? 1.0 : 0.0);
+  // row r of S U: 15 plain reads; lane 15 reads zero words (its row of U' is zero).  An
+  // inactive point's columns are the unit vectors, U = I, and so is U' (the 1/2 weights
+  // below are exact)
+  lds_zero_t* const src = lane_ok ? (lds_zero_t*)&Ut[p][r][0] : zl;
   double R[NS];
 #pragma unroll
-  for (int m = 0; m < NS; ++m) R[m] = fma(a2, Ut[p][r2][m], a1 * Ut[p][r1][m]);
+  for (int m = 0; m < NS; ++m) R[m] = src[m];
   // columns: (S U) S^-1 -- plain coordinates are renamed, (m, q, p) recombined
   static_for<NS>([&](auto N) {
     constexpr int nn = decltype(N)::value;
@@ -751,6 +768,33 @@ __device__ __forceinline__ void sym16_epilogue(double t, double z, double s00, d
                                                uint32_t* __restrict__ status, double (&Ut)[S16_PPW][NS][16]
                                                S16_PROF_ARG);
 
+// load_point for a lane of this kernel: column f of the lane's point is read at the
+// wave-uniform address prm + f ld + i0 (64-bit, SGPRs) plus the lane's 32-bit byte offset
+// po8 (8 x its clamped point index within the wave): a global load with an SGPR base and
+// a VGPR offset, no per-lane 64-bit add per column (LP square and bang-bang: every load;
+// smooth JP: the first load_point, its chunk loop keeps the 64-bit adds).
+typedef __attribute__((address_space(1))) char s16_gchar;
+typedef __attribute__((address_space(1))) double s16_gdouble;
+template <int PROTO>
+__device__ __forceinline__ PointP load_point16(const double* __restrict__ prm, int64_t ldp, int64_t i0,
+                                               unsigned po8) {
+  unsigned off = po8;                        // widened where it is used: the offset operand is
+  if constexpr (PROTO != RYD_PROTO_SMOOTH_JP)   // matched within the block of the loads (smooth
+    asm("" : "+v"(off));                     // JP: its chunk loop's 3 loads; costs 5 VGPRs there)
+  PointP q = load_point_with<PROTO>([&](int f) {
+    const char* base = reinterpret_cast<const char*>(prm + ((int64_t)f * ldp + i0));
+    asm("" : "+s"(base));                    // stays a scalar base: not re-associated with po8
+    // the barrier loses the pointer's address space; as a global pointer again the load
+    // takes the SGPR base and the lane offset directly (global_load ..., v_off, s[base])
+    const s16_gchar* gbase = (const s16_gchar*)base;
+    return *reinterpret_cast<const s16_gdouble*>(gbase + off);
+  });
+  q.prm = prm;
+  q.ld = ldp;
+  q.i = i0 + (int64_t)(po8 >> 3);
+  return q;
+}
+
 template <int PROTO>
 __global__ __launch_bounds__(S16_BLOCK) __attribute__((amdgpu_waves_per_eu(PROTO == RYD_PROTO_BANGBANG ? 3 : RYD_S16_WAVES, 8))) void
 lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st,
@@ -764,19 +808,21 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
   s16_ts[8] = (double)__builtin_amdgcn_s_memrealtime();
   S16_MARK(0);
 #endif
-  __shared__ double Zl[10];                  // zero words: squaring accumulator clears
+  __shared__ double Zl[16];                  // zero words: squaring accumulator clears, lane 15's row
   const int l = threadIdx.x;
   const int p = l >> 4, r = l & 15;
-  if (l < 10) Zl[l] = 0.0;                   // same wave: ordered before the first squaring
-  const int64_t blk = xcd_block(blockIdx.x, gridDim.x);
-  const int64_t ip = blk * S16_PPW + p;
-  const int64_t i = ip < n ? ip : n - 1;
-  bool valid, frame_ok;
-  {
-    const PointP q0 = load_point<PROTO>(prm, ldp, i);
-    valid = point_valid<PROTO>(q0, n_steps);
-    frame_ok = !(PROTO == RYD_PROTO_LP_SQUARE) || !valid || fabs(q0.xr * q0.xr + q0.xi * q0.xi - 1.0) <= 1e-14;
-  }
+  if (l < 16) Zl[l] = 0.0;                   // same wave: ordered before the first squaring
+  // the wave's first point (uniform, 64-bit) and this lane's byte offset from it, clamped
+  // to the batch: every parameter address is an SGPR base plus this 32-bit offset
+  const int64_t b0 = xcd_block(blockIdx.x, gridDim.x) * S16_PPW;
+  const int64_t i0 = b0 < n ? b0 : n - 1;    // a wave past the batch (padded grid) reads point n-1
+  const int64_t last = n - 1 - i0;           // >= 0
+  const unsigned po8 = 8u * (unsigned)min(p, last < S16_PPW - 1 ? (int)last : S16_PPW - 1);
+  // loaded and validated once; the segment-0 build takes its inputs from here
+  const PointP q0 = load_point16<PROTO>(prm, ldp, i0, po8);
+  const bool valid = point_valid<PROTO>(q0, n_steps);
+  const bool frame_ok =
+      !(PROTO == RYD_PROTO_LP_SQUARE) || !valid || fabs(q0.xr * q0.xr + q0.xi * q0.xi - 1.0) <= 1e-14;
   S16_MARK(1);
   S16_PRIO(3);
 #ifndef RYD_S16_TAIL_PRIO
@@ -804,7 +850,7 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
     double ph_c, ph_s, dt;
     double th_c, th_s, dc, ds;               // cos/sin of lane r's modulation angle; chunk step
     {
-      const PointP q = load_point<PROTO>(prm, ldp, i);
+      const PointP& q = q0;
       dt = q.tau / (double)n_steps;
       int rep0;
       build16(u, Ut, q, valid, valid, q.Om, q.Dl, dt, p, r, 0, rep0, nuse, nexec, nsq, over_cap,
@@ -831,7 +877,7 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
       {
         const double* pp = prm;
         asm volatile("" : "+s"(pp));
-        const PointP q = load_point<PROTO>(pp, ldp, i);
+        const PointP q = load_point16<PROTO>(pp, ldp, i0, po8);
         double cth = th_c;
         if (s0 + 16 > nseg) {                // last chunk: lanes past the end take segment nseg-1
           double st, ct;
@@ -913,9 +959,7 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
       // first application of U' is a column read: t = U' e_(1,1) (segment-order lane 5),
       // z = column 1 of the |01> row, s00 = U'_00 -- what seg_apply gives on the unit
       // vectors (0 * x = 0 for finite rows) without its 20 DPP FMAs and the rotation.
-      const double* pp = prm;
-      asm volatile("" : "+s"(pp));
-      const PointP q = load_point<PROTO>(pp, ldp, i);
+      const PointP& q = q0;
       double a, c, sn, dl, dt;
       bool hold;
       seg_polar<PROTO>(q, 0, n_steps, frame_ok, a, c, sn, dl, dt, hold);
@@ -940,11 +984,12 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
       wave_sync();
     }
     for (int s = 1; s < nseg; ++s) {
-      // re-read the point's scalars every segment (L1 hits) instead of keeping them
-      // live: the Chebyshev phase needs the registers
+      // re-read the segment's scalars (L1 hits) instead of keeping them live: the
+      // Chebyshev phase needs the registers.  Only what seg_polar reads is loaded here
+      // (LP square: amplitude, duration, xi); a rebuild loads the whole point itself.
       const double* pp = prm;
       asm volatile("" : "+s"(pp));
-      const PointP q = load_point<PROTO>(pp, ldp, i);
+      const PointP q = load_point16<PROTO>(pp, ldp, i0, po8);
       double a, c, sn, dl, dt;
       bool hold;
       seg_polar<PROTO>(q, s, n_steps, frame_ok, a, c, sn, dl, dt, hold);
@@ -963,7 +1008,10 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
           Sc[p][1] = nsq;
         }
         int nu = 0, nq = 0;
-        build16(u, Ut, q, valid, need, a, dl, dt, p, r, KEEP, rep, nu, nexec, nq, over_cap,
+        const double* pb = pp;               // bang-bang rebuilds every segment: the same loads
+        if constexpr (PROTO == RYD_PROTO_LP_SQUARE) asm volatile("" : "+s"(pb));   // loaded on this path only
+        const PointP qb = load_point16<PROTO>(pb, ldp, i0, po8);
+        build16(u, Ut, qb, valid, need, a, dl, dt, p, r, KEEP, rep, nu, nexec, nq, over_cap,
                 (lds_zero_t*)Zl S16_PROF_PASS);
         nrep = wave_max(rep);
         t = Sv[p][r][0];
@@ -981,7 +1029,7 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
         wave_sync();
         const double* pq = prm;
         asm volatile("" : "+s"(pq));
-        seg_polar<PROTO>(load_point<PROTO>(pq, ldp, i), s, n_steps, frame_ok, a, c, sn, dl, dt, hold);
+        seg_polar<PROTO>(load_point16<PROTO>(pq, ldp, i0, po8), s, n_steps, frame_ok, a, c, sn, dl, dt, hold);
       }
       if (hold) {
         c = cp;
