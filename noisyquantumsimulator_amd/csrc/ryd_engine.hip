@@ -194,9 +194,10 @@ __device__ __forceinline__ Seg segment(const PointP& q, int s, int n_steps, int 
 
 // Gershgorin bound on the spectrum of the two-atom H for one segment:
 // diag E(a1,a2) = e(a1)+e(a2)+V[rr], e = {0, delta1, -Delta}; |Omega|/2 per excitable atom.
-__device__ __forceinline__ void h_bounds(const Seg& g, double V, double d1, double& emin, double& emax) {
-  const double e[3] = {0.0, d1, -g.dl};
-  const double w = 0.5 * sqrt(g.om_re * g.om_re + g.om_im * g.om_im);
+// h_bounds_w: the same with the half-width w = |Omega| / 2 supplied by the caller.
+__device__ __forceinline__ void h_bounds_w(double w, double dl, double V, double d1, double& emin,
+                                           double& emax) {
+  const double e[3] = {0.0, d1, -dl};
   emin = 1e300;
   emax = -1e300;
 #pragma unroll
@@ -208,6 +209,10 @@ __device__ __forceinline__ void h_bounds(const Seg& g, double V, double d1, doub
       emin = fmin(emin, E - r);
       emax = fmax(emax, E + r);
     }
+}
+
+__device__ __forceinline__ void h_bounds(const Seg& g, double V, double d1, double& emin, double& emax) {
+  h_bounds_w(0.5 * sqrt(g.om_re * g.om_re + g.om_im * g.om_im), g.dl, V, d1, emin, emax);
 }
 
 // Chebyshev degree for tail J_K(x) < 1e-17 (Airy asymptotics; exact series test for small x).
@@ -2371,6 +2376,14 @@ bool use_sym16(const ryd_batch_desc* d) {
           d->protocol == RYD_PROTO_SMOOTH_JP);
 }
 
+// RYD_S16_STORE64=1 makes the sym16 kernel form its output addresses per lane in 64 bits
+// for every launch (the form it takes anyway when a leading dimension is too large for a
+// 32-bit lane offset): tests run both
+bool sym16_store32_enabled() {
+  const char* e = getenv("RYD_S16_STORE64");
+  return !(e && e[0] == '1');
+}
+
 // LP shaped, identical atoms, the auto method: the 16-lane DPP-row state-vector kernel
 // (ryd_shaped16.inc); RYD_SHAPED16=0 keeps lindblad_cheb_kernel (the cross-check)
 bool use_shaped16(const ryd_batch_desc* d) {
@@ -2606,15 +2619,19 @@ int launch(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, do
   }
   if (use_sym16(d)) {
     using SFn = void (*)(const double*, int64_t, int64_t, double*, int64_t, double*, int64_t, uint32_t*,
-                         int, int);
+                         int, int, int);
     SFn f = d->protocol == RYD_PROTO_LP_SQUARE ? lindblad_sym16_kernel<RYD_PROTO_LP_SQUARE>
             : d->protocol == RYD_PROTO_SMOOTH_JP ? lindblad_sym16_kernel<RYD_PROTO_SMOOTH_JP>
                                                   : lindblad_sym16_kernel<RYD_PROTO_BANGBANG>;
     const int64_t blocks = (n + S16_PPW - 1) / S16_PPW;
     if (blocks > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
     int ns = d->n_steps, sh = d->shape;
+    // the output stores take a wave-uniform base plus a 32-bit lane byte offset where the
+    // largest one fits: 8 (15 + 3 lds) on the state rows, 8 (15 ldm + 3) on the summary
+    int st32 = sym16_store32_enabled() && lds >= 0 && ldm >= 0 && lds <= (0x1fffffffLL - 15) / 3 &&
+               ldm <= (0x1fffffffLL - 3) / 15;
     void* args[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&ds, (void*)&lds, (void*)&dm,
-                    (void*)&ldm, (void*)&dstat, (void*)&ns, (void*)&sh};
+                    (void*)&ldm, (void*)&dstat, (void*)&ns, (void*)&sh, (void*)&st32};
     HIPCHK(hipLaunchKernel((const void*)f, dim3((unsigned)blocks), dim3(S16_BLOCK), args, 0, stream));
     return RYD_OK;
   }

@@ -92,6 +92,20 @@ __device__ __forceinline__ int64_t xcd_block(int64_t b, int64_t nb) {
   return ((k / 4) * 8 + x) * 4 + (k % 4);
 }
 
+// wave_max with the partner lane as the DPP operand of the max itself: every lane of these
+// four permutations has a valid source, so the move's `old` value never shows and the
+// builtin without one (bound_ctrl) lets the compiler fold each move into its v_max_i32_dpp
+// (wave_max: a copy, a DPP move and the max per step).  Call with every lane active.
+__device__ __forceinline__ int wave_max16(int v) {
+  v = max(v, __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
+  v = max(v, __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
+  v = max(v, __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true));   // row_half_mirror
+  v = max(v, __builtin_amdgcn_mov_dpp(v, 0x140, 0xF, 0xF, true));   // row_mirror
+  const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
+  const int c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
+  return max(max(a, b), max(c, d));
+}
+
 // lane K of each 16-lane row, broadcast to the whole row (DPP row_newbcast, gfx90a+)
 template <int K>
 __device__ __forceinline__ double row_bcast(double v) {
@@ -402,6 +416,8 @@ __device__ __forceinline__ void apply_Lsym_re(const Gen& a, double vs, const dou
 // in h = x/2, so kt = 1 + #{j <= 17 : h >= TH_j} with TH_j the smallest double whose
 // j-th term reaches 1e-17 (exact rational check, tools/cheb_thresholds.py): 17 compares
 // instead of the 34-multiply product chain (identical kt on 2e5 random arguments).
+// BOUNDED: the caller guarantees x <= X_BASE_SYM (build16's scaled argument).
+template <bool BOUNDED = false>
 __device__ __forceinline__ int cheb_terms_small(double x) {
   static_assert(X_BASE_SYM <= 1.0, "cheb_terms_small covers x <= 1 (17 terms)");
   constexpr double TH[17] = {1e-17, 4.4721359549995795e-09, 3.914867641168864e-06, 0.00012446659545769568,
@@ -410,10 +426,15 @@ __device__ __forceinline__ int cheb_terms_small(double x) {
                              0.1398168813097236, 0.20262580209060138, 0.2790704614462359,
                              0.36912378048400807, 0.47253426642798413, 0.5888961629494429,
                              0.7177037357024775};
+  // build16 passes y <= X_BASE_SYM (up to the rounding of x / X_BASE_SYM; exact at 0.5), so
+  // a threshold above X_BASE_SYM / 2 is never reached there and its compare is left out:
+  // 12 compares of the 17 at X_BASE_SYM = 0.5, the same count
+  constexpr double HMAX = BOUNDED ? 0.5 * X_BASE_SYM * (1.0 + 1e-12) : 1.0;
   const double h = 0.5 * x;
   int k = 1;
 #pragma unroll
-  for (int j = 0; j < 17; ++j) k += (h >= TH[j]) ? 1 : 0;
+  for (int j = 0; j < 17; ++j)
+    if (TH[j] <= HMAX) k += (h >= TH[j]) ? 1 : 0;
   return k;
 }
 
@@ -431,11 +452,20 @@ constexpr int S16_KS = 20;
 // An inactive lane (lane 15, an invalid or empty point) runs the recurrence with zero
 // coefficients and J_0 = S = 1, which leaves exactly e_r (nothing for lane 15) without
 // a select per coordinate; the caller zeroes an inactive point's generator.
+// (double)k of a wave-uniform order 1 <= k < 2^20 put together on the scalar unit (exponent
+// from the leading bit, the mantissa shifted into the high word): the same double as the
+// conversion, which would be a VALU op per order of the recurrence
+__device__ __forceinline__ double order_f64(int k) {
+  const int e = 31 - __builtin_clz((unsigned)k);
+  const unsigned hi = ((unsigned)(1023 + e) << 20) | (((unsigned)k << (20 - e)) & 0xFFFFFu);
+  return __builtin_bit_cast(double, (unsigned long long)hi << 32);
+}
+
 template <typename Apply>
 __device__ __forceinline__ void cheb_unit16(double (&out)[NS], int r, double x, bool active, Apply apply2Y,
-                                            int& nuse, int& nexec) {
-  const int kt = active ? cheb_terms_small(x) : -1;
-  const int kmax = wave_max(kt);
+                                            int& nuse, int& nexec, lds_zero_t* zl) {
+  const int kt = active ? cheb_terms_small<true>(x) : -1;
+  const int kmax = wave_max16(kt);
   if (kmax < 0) {                            // no active lane in the wave: identity columns
     asm volatile("" : "+v"(r));
 #pragma unroll
@@ -443,9 +473,20 @@ __device__ __forceinline__ void cheb_unit16(double (&out)[NS], int r, double x, 
     return;
   }
   const int kcut = (kmax + 1) & ~1;
+  // the 30 accumulators start from LDS zero words, as the squarings' do: the reads land
+  // behind the Miller-only orders and the first division instead of 30 VALU moves
   double bA[NS], bB[NS];
+  asm volatile("" ::: "memory");             // re-read, not forwarded or merged
 #pragma unroll
-  for (int e = 0; e < NS; ++e) bA[e] = bB[e] = 0.0;
+  for (int e = 0; e < NS; ++e) {
+    bA[e] = zl[e];
+    asm volatile("" ::: "memory");
+  }
+#pragma unroll
+  for (int e = 0; e < NS; ++e) {
+    bB[e] = zl[e];
+    asm volatile("" ::: "memory");
+  }
   double sel[4];                             // RYD_MASKED_ADD == 3: 1.0 on lanes = q mod 4
   {
     const int q = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) & 3;
@@ -466,11 +507,11 @@ __device__ __forceinline__ void cheb_unit16(double (&out)[NS], int r, double x, 
     Jp1 = J;
   }
   for (int k = S16_KS - 2; k > kcut; k -= 2) {
-    const double Jk = fma(i2x * (double)(k + 1), Jp1, -Jp2);
+    const double Jk = fma(i2x * order_f64(k + 1), Jp1, -Jp2);
     Jp2 = Jp1;
     Jp1 = Jk;
     S = fma(2.0, Jk, S);
-    const double Jk1 = fma(i2x * (double)k, Jp1, -Jp2);
+    const double Jk1 = fma(i2x * order_f64(k), Jp1, -Jp2);
     Jp2 = Jp1;
     Jp1 = Jk1;
   }
@@ -478,26 +519,26 @@ __device__ __forceinline__ void cheb_unit16(double (&out)[NS], int r, double x, 
   // application adds exact zeros to bB = c_k e_r and is left out (same bits).
   {
     const int k = kcut;
-    const double Jk = fma(i2x * (double)(k + 1), Jp1, -Jp2);
+    const double Jk = fma(i2x * order_f64(k + 1), Jp1, -Jp2);
     Jp2 = Jp1;
     Jp1 = Jk;
     S = fma(2.0, Jk, S);
     unit_add(bB, k <= kt ? 2.0 * Jk : 0.0);
-    const double Jk1 = fma(i2x * (double)k, Jp1, -Jp2);
+    const double Jk1 = fma(i2x * order_f64(k), Jp1, -Jp2);
     Jp2 = Jp1;
     Jp1 = Jk1;
     unit_add(bA, k - 1 <= kt ? 2.0 * Jk1 : 0.0);
     apply2Y(bB, bA);
   }
   for (int k = kcut - 2; k >= 2; k -= 2) {
-    double Jk = fma(i2x * (double)(k + 1), Jp1, -Jp2);
+    double Jk = fma(i2x * order_f64(k + 1), Jp1, -Jp2);
     Jp2 = Jp1;
     Jp1 = Jk;
     S = fma(2.0, Jk, S);
     const double ck = k <= kt ? 2.0 * Jk : 0.0;
     unit_add(bB, ck);
     apply2Y(bA, bB);
-    double Jk1 = fma(i2x * (double)k, Jp1, -Jp2);
+    double Jk1 = fma(i2x * order_f64(k), Jp1, -Jp2);
     Jp2 = Jp1;
     Jp1 = Jk1;
     const double ck1 = k - 1 <= kt ? 2.0 * Jk1 : 0.0;
@@ -556,10 +597,10 @@ __host__ __device__ constexpr int seg_old(int n) {      // plain segment coordin
 // The last min(s, keep) squaring levels are left out: U_built = exp(L dt)^(1 / 2^rep),
 // rep = min(s, keep), and the caller applies it 2^rep times per segment (for the few
 // states of LP square, 2^rep - 1 extra row updates cost less than `keep` squarings).
-// nsq counts the full depth s (RYD_S_NSQUARE).
+// nsq counts the full depth s (RYD_S_NSQUARE).  nrep = the wave's largest rep.
 __device__ __forceinline__ void build16(double (&u)[NS], double (&Ut)[S16_PPW][NS][16], const PointP& q,
                                         bool valid, bool count, double a, double dl, double dt, int p, int r,
-                                        int keep, int& rep, int& nuse, int& nexec, int& nsq,
+                                        int keep, int& rep, int& nrep, int& nuse, int& nexec, int& nsq,
                                         bool& over_cap, lds_zero_t* zl S16_PROF_ARG) {
   const bool lane_ok = r < NS;
   Seg g;
@@ -570,8 +611,20 @@ __device__ __forceinline__ void build16(double (&u)[NS], double (&Ut)[S16_PPW][N
   double rsum = 0.0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) rsum += fabs(q.gA[k]) + fabs(q.gB[k]);
+  // h_bounds' half-width 0.5 sqrt(a a + 0 0): the correctly rounded root of the rounded
+  // square is |a| itself as long as a a neither overflows nor leaves the normal range
+  // (or a = 0), so a wave of such amplitudes takes 0.5 |a| -- the same double -- and the
+  // root stays behind a wave-uniform branch for the rest (NaN included)
+  const double fa = fabs(a);
+  const bool plain = (fa >= 0x1p-500 && fa <= 0x1p500) || fa == 0.0;
+  double hw = 0.5 * fa;
+  if (__builtin_amdgcn_ballot_w64(!plain) != 0) {
+    double ar = g.om_re;
+    asm volatile("" : "+v"(ar));             // stays a branch: the root is not speculated into a select
+    hw = 0.5 * sqrt(ar * ar + g.om_im * g.om_im);
+  }
   double emin, emax;
-  h_bounds(g, q.V, q.d1, emin, emax);
+  h_bounds_w(hw, g.dl, q.V, q.d1, emin, emax);
   const double omega = (emax - emin) + rsum;
   const double x = omega * dt;
   const bool capped = valid && !(x <= 1e12);
@@ -607,15 +660,23 @@ __device__ __forceinline__ void build16(double (&u)[NS], double (&Ut)[S16_PPW][N
   double v[NS];
   const int nuse0 = nuse;
   cheb_unit16(v, r, y, act && lane_ok,
-              [&](const double (&b)[NS], double (&o)[NS]) { apply_Lsym_re(A, vs, b, o); }, nuse, nexec);
+              [&](const double (&b)[NS], double (&o)[NS]) { apply_Lsym_re(A, vs, b, o); }, nuse, nexec, zl);
   if (!count) nuse = nuse0;                  // each distinct propagator counted once
   S16_MARK(2);
   S16_PRIO(2);
   // ---- (2) squarings, column-held, DPP broadcasts within the row
-  const int smx = wave_max(sq);
+  // one reduction of the full depth serves both loops: sq and rep are monotone in sqf, so
+  // their maxima over the wave are the same functions of the largest depth
+  const int sfm = wave_max16(sqf);
+  nrep = sfm > keep ? keep : sfm;
+#ifndef RYD_S16_SQ_CAP
+  const int smx = sfm > keep ? sfm - keep : 0;
+#else
+  const int smx = min(sfm > keep ? sfm - keep : 0, RYD_S16_SQ_CAP);
+#endif
   {
-    double w[NS];                            // ping-pong: v -> w -> v
     for (int it = 0; it < smx; it += 2) {
+      double w[NS];                          // ping-pong: v -> w -> v (nothing carried in w)
       if (RYD_S16_PRIO_SPLIT && it == ((smx >> 1) & ~1)) S16_PRIO(1);   // second half of the squarings
       if (it < sq) square_cols16(v, w, zl);
       if (it + 1 < sq) {
@@ -761,12 +822,12 @@ __device__ __forceinline__ void seg_apply(const double (&u)[NS], const SegRow01&
   z = acc1;
 }
 
-__device__ __forceinline__ void sym16_epilogue(double t, double z, double s00, double cp, double sp, bool valid,
-                                               bool over_cap, int nuse, int nexec, int nsq, int l, int p,
-                                               int64_t blk, int64_t n, double* __restrict__ st, int64_t lds,
-                                               double* __restrict__ sm, int64_t ldm,
-                                               uint32_t* __restrict__ status, double (&Ut)[S16_PPW][NS][16]
-                                               S16_PROF_ARG);
+__device__ __forceinline__ void sym16_epilogue(double t, double z, double s00, double cp, double sp,
+                                               const SegRot& rw, bool valid, bool over_cap, int nuse, int nexec,
+                                               int nsq, int l, int p, int64_t blk, int64_t n,
+                                               double* __restrict__ st, int64_t lds, double* __restrict__ sm,
+                                               int64_t ldm, uint32_t* __restrict__ status, bool st32,
+                                               double (&Ut)[S16_PPW][NS][16] S16_PROF_ARG);
 
 // load_point for a lane of this kernel: column f of the lane's point is read at the
 // wave-uniform address prm + f ld + i0 (64-bit, SGPRs) plus the lane's 32-bit byte offset
@@ -799,7 +860,7 @@ template <int PROTO>
 __global__ __launch_bounds__(S16_BLOCK) __attribute__((amdgpu_waves_per_eu(PROTO == RYD_PROTO_BANGBANG ? 3 : RYD_S16_WAVES, 8))) void
 lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st,
                       int64_t lds, double* __restrict__ sm, int64_t ldm, uint32_t* __restrict__ status,
-                      int n_steps, int shape) {
+                      int n_steps, int shape, int st32) {
   __shared__ __attribute__((aligned(16))) double Ut[S16_PPW][NS][16];     // transpose, then output staging
   static_assert(sizeof(Ut) >= sizeof(double) * S16_PPW * 4 * NC, "output staging must fit in Ut");
   (void)shape;
@@ -842,6 +903,7 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
   int nuse = 0, nexec = 0, nsq = 0;        // flop counters (series terms, squarings)
   bool over_cap = false;
   const int nseg = n_segments<PROTO>(n_steps);
+  SegRot rw_out = {};                        // LP square: segment 1's lane weights serve the epilogue too
 
   if constexpr (PROTO == RYD_PROTO_SMOOTH_JP) {
     // one propagator (every segment has amplitude Omega and duration tau / n_steps),
@@ -853,7 +915,8 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
       const PointP& q = q0;
       dt = q.tau / (double)n_steps;
       int rep0;
-      build16(u, Ut, q, valid, valid, q.Om, q.Dl, dt, p, r, 0, rep0, nuse, nexec, nsq, over_cap,
+      int nrep0;
+      build16(u, Ut, q, valid, valid, q.Om, q.Dl, dt, p, r, 0, rep0, nrep0, nuse, nexec, nsq, over_cap,
               (lds_zero_t*)Zl S16_PROF_PASS);
       // the modulation angle theta_s = w_mod (s dt + dt/2) - phi_off of segment s = s0 + r
       // (RG/simulation.py:1698-1731) advances by 16 w_mod dt per chunk: one rotation of
@@ -953,6 +1016,7 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
     __shared__ int Sc[S16_PPW][2];
     constexpr int KEEP = PROTO == RYD_PROTO_LP_SQUARE ? RYD_LP_UNSQUARED : 0;
     int rep = 0, nrep = 0;                   // unsquared levels of the current propagator
+    SegRow01 k1 = {};                        // the |01> row of the current propagator
     if (nseg > 0) {
       // Segment 0 always builds (an all-invalid wave builds identity rows).  The inputs
       // |11>, |01>, |00> are basis states that every frame rotation leaves alone, so the
@@ -963,14 +1027,15 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
       double a, c, sn, dl, dt;
       bool hold;
       seg_polar<PROTO>(q, 0, n_steps, frame_ok, a, c, sn, dl, dt, hold);
-      build16(u, Ut, q, valid, valid, a, dl, dt, p, r, KEEP, rep, nuse, nexec, nsq, over_cap,
+      build16(u, Ut, q, valid, valid, a, dl, dt, p, r, KEEP, rep, nrep, nuse, nexec, nsq, over_cap,
               (lds_zero_t*)Zl S16_PROF_PASS);
-      nrep = wave_max(rep);
-      if (r == 0) {                          // segment the propagator was built for
-        Sp[p][5] = a;
-        Sp[p][6] = dt;
+      if constexpr (PROTO != RYD_PROTO_LP_SQUARE) {
+        if (r == 0) {                        // segment the propagator was built for
+          Sp[p][5] = a;
+          Sp[p][6] = dt;
+        }
       }
-      const SegRow01 k1 = seg_row01(u, r);
+      k1 = seg_row01(u, r);
       t = u[sym_index(1, 1)];
       z = k1.o[1];
       s00 = k1.u00;
@@ -987,58 +1052,74 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
       // re-read the segment's scalars (L1 hits) instead of keeping them live: the
       // Chebyshev phase needs the registers.  Only what seg_polar reads is loaded here
       // (LP square: amplitude, duration, xi); a rebuild loads the whole point itself.
-      const double* pp = prm;
-      asm volatile("" : "+s"(pp));
-      const PointP q = load_point16<PROTO>(pp, ldp, i0, po8);
       double a, c, sn, dl, dt;
-      bool hold;
-      seg_polar<PROTO>(q, s, n_steps, frame_ok, a, c, sn, dl, dt, hold);
-      const bool need = valid && !(a == Sp[p][5] && dt == Sp[p][6]);
-      if (__builtin_amdgcn_ballot_w64(need) != 0) {
-        // Every point of the wave rebuilds: a point whose segment did not change gets
-        // the same propagator bit for bit (its series and squarings do not depend on
-        // its neighbours), so the previous row need not stay live through the build.
-        Sv[p][r][0] = t;
-        Sv[p][r][1] = z;
-        if (r == 0) {
-          Sp[p][0] = s00;
-          Sp[p][1] = cp;
-          Sp[p][2] = sp;
-          Sc[p][0] = nuse;
-          Sc[p][1] = nsq;
+      bool hold = false;
+      // LP square with every xi of the wave on the unit circle (or its row invalid): the
+      // segment has segment 0's amplitude and duration (valid: both finite), no rebuild, and
+      // its phase is q0's xi, which stays in registers through the build (LP square has them
+      // to spare: 122 VGPRs) -- no global load, no LDS exchange.  The general path (a non-unit
+      // xi somewhere in the wave; bang-bang always) stays as it was.
+      bool general = true;
+      if constexpr (PROTO == RYD_PROTO_LP_SQUARE) {
+        general = __builtin_amdgcn_ballot_w64(!frame_ok) != 0;
+        c = q0.xr;
+        sn = q0.xi;
+      }
+      if (general) {
+        const double* pp = prm;
+        asm volatile("" : "+s"(pp));
+        const PointP q = load_point16<PROTO>(pp, ldp, i0, po8);
+        seg_polar<PROTO>(q, s, n_steps, frame_ok, a, c, sn, dl, dt, hold);
+        // LP square: segment 0 was built for (Omega, tau), the same loads
+        const bool need = PROTO == RYD_PROTO_LP_SQUARE ? valid && !(a == q.Om && dt == q.tau)
+                                                       : valid && !(a == Sp[p][5] && dt == Sp[p][6]);
+        if (__builtin_amdgcn_ballot_w64(need) != 0) {
+          // Every point of the wave rebuilds: a point whose segment did not change gets
+          // the same propagator bit for bit (its series and squarings do not depend on
+          // its neighbours), so the previous row need not stay live through the build.
+          Sv[p][r][0] = t;
+          Sv[p][r][1] = z;
+          if (r == 0) {
+            Sp[p][0] = s00;
+            Sp[p][1] = cp;
+            Sp[p][2] = sp;
+            Sc[p][0] = nuse;
+            Sc[p][1] = nsq;
+          }
+          int nu = 0, nq = 0;
+          const double* pb = pp;               // bang-bang rebuilds every segment: the same loads
+          if constexpr (PROTO == RYD_PROTO_LP_SQUARE) asm volatile("" : "+s"(pb));   // loaded on this path only
+          const PointP qb = load_point16<PROTO>(pb, ldp, i0, po8);
+          build16(u, Ut, qb, valid, need, a, dl, dt, p, r, KEEP, rep, nrep, nu, nexec, nq, over_cap,
+                  (lds_zero_t*)Zl S16_PROF_PASS);
+          t = Sv[p][r][0];
+          z = Sv[p][r][1];
+          s00 = Sp[p][0];
+          cp = Sp[p][1];
+          sp = Sp[p][2];
+          nuse = Sc[p][0] + nu;
+          nsq = Sc[p][1] + nq;
+          wave_sync();
+          if constexpr (PROTO != RYD_PROTO_LP_SQUARE) {   // LP square has no third segment to compare
+            if (r == 0) {
+              Sp[p][5] = a;
+              Sp[p][6] = dt;
+            }
+            wave_sync();
+          }
+          const double* pq = prm;
+          asm volatile("" : "+s"(pq));
+          seg_polar<PROTO>(load_point16<PROTO>(pq, ldp, i0, po8), s, n_steps, frame_ok, a, c, sn, dl, dt, hold);
+          k1 = seg_row01(u, r);                // the |01> row is not kept live across a build
         }
-        int nu = 0, nq = 0;
-        const double* pb = pp;               // bang-bang rebuilds every segment: the same loads
-        if constexpr (PROTO == RYD_PROTO_LP_SQUARE) asm volatile("" : "+s"(pb));   // loaded on this path only
-        const PointP qb = load_point16<PROTO>(pb, ldp, i0, po8);
-        build16(u, Ut, qb, valid, need, a, dl, dt, p, r, KEEP, rep, nu, nexec, nq, over_cap,
-                (lds_zero_t*)Zl S16_PROF_PASS);
-        nrep = wave_max(rep);
-        t = Sv[p][r][0];
-        z = Sv[p][r][1];
-        s00 = Sp[p][0];
-        cp = Sp[p][1];
-        sp = Sp[p][2];
-        nuse = Sc[p][0] + nu;
-        nsq = Sc[p][1] + nq;
-        wave_sync();
-        if (r == 0) {
-          Sp[p][5] = a;
-          Sp[p][6] = dt;
-        }
-        wave_sync();
-        const double* pq = prm;
-        asm volatile("" : "+s"(pq));
-        seg_polar<PROTO>(load_point16<PROTO>(pq, ldp, i0, po8), s, n_steps, frame_ok, a, c, sn, dl, dt, hold);
       }
       if (hold) {
         c = cp;
         sn = sp;
       }
       const double cr = cp * c + sp * sn, sr = sp * c - cp * sn;
-      // (rotation weights and the |01> row are not kept live across an in-loop build)
-      const SegRow01 k1 = seg_row01(u, r);
-      rotate_state(t, z, cr, sr, seg_rot(r));
+      rw_out = seg_rot(r);                   // (rotation weights are not kept live across a build)
+      rotate_state(t, z, cr, sr, rw_out);
       seg_apply(u, k1, t, z, s00);
       // the unsquared levels: 2^rep - 1 more applications of the built factor, frame fixed
       for (int j = 1; j < (1 << nrep); ++j) {
@@ -1056,22 +1137,23 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
     int pl = lid >> 4;
     asm volatile("" : "+v"(pl));
     const int64_t b2 = xcd_block(blockIdx.x, gridDim.x);
-    return sym16_epilogue(t, z, s00, cp, sp, valid, over_cap, nuse, nexec, nsq, lid, pl, b2, n, st, lds, sm, ldm,
-                          status, Ut S16_PROF_PASS);
+    if constexpr (PROTO != RYD_PROTO_LP_SQUARE) rw_out = seg_rot(lid & 15);
+    return sym16_epilogue(t, z, s00, cp, sp, rw_out, valid, over_cap, nuse, nexec, nsq, lid, pl, b2, n, st, lds, sm,
+                          ldm, status, st32 != 0, Ut S16_PROF_PASS);
   }
 }
 
-__device__ __forceinline__ void sym16_epilogue(double t, double z, double s00, double cp, double sp, bool valid,
-                                               bool over_cap, int nuse, int nexec, int nsq, int l, int p,
-                                               int64_t blk, int64_t n, double* __restrict__ st, int64_t lds,
-                                               double* __restrict__ sm, int64_t ldm,
-                                               uint32_t* __restrict__ status, double (&Ut)[S16_PPW][NS][16]
-                                               S16_PROF_ARG) {
+__device__ __forceinline__ void sym16_epilogue(double t, double z, double s00, double cp, double sp,
+                                               const SegRot& rw, bool valid, bool over_cap, int nuse, int nexec,
+                                               int nsq, int l, int p, int64_t blk, int64_t n,
+                                               double* __restrict__ st, int64_t lds, double* __restrict__ sm,
+                                               int64_t ldm, uint32_t* __restrict__ status, bool st32,
+                                               double (&Ut)[S16_PPW][NS][16] S16_PROF_ARG) {
   const int r = l & 15;
   const bool lane_ok = r < NS;
   const int64_t ip = blk * S16_PPW + p;
   const int64_t i = ip < n ? ip : n - 1;
-  rotate_state(t, z, cp, sp, seg_rot(r));
+  rotate_state(t, z, cp, sp, rw);
   // segment order -> triangle coordinates: (3,3) = (p + m)/2, (3,4) = q/2, (4,4) = (p - m)/2
   {
     const double mv = row_bcast<SEG_M>(t), pv = row_bcast<SEG_P>(t);
@@ -1104,18 +1186,35 @@ __device__ __forceinline__ void sym16_epilogue(double t, double z, double s00, d
   const int64_t i0 = blk * S16_PPW;
   {
     const int cc = l & 15, pp = cc >> 2, k = cc & 3;
-    double* dst = st + 4 * i0 + cc;
     const bool in = i0 + pp < n;
     double v[7];
 #pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      const int row = (l >> 4) + 4 * j;
-      v[j] = row < NC ? Ro[pp][k][row] : 0.0;
-    }
+    for (int j = 0; j < 7; ++j)              // rows 25 .. 27 (j = 6, lanes >= 16): read inside Ut, never stored
+      v[j] = (&Ro[pp][k][0])[(l >> 4) + 4 * j];
+    static_assert(NC == 25, "rows l/16 + 4 j: j < 6 always inside, j = 6 on the first 16 lanes only");
+    if (st32) {
+      // the wave-uniform address st + 4 i0 + 4 j lds (SGPRs) plus the lane's 32-bit byte
+      // offset 8 (cc + (l / 16) lds); launch() has checked that the offset fits
+      const unsigned lo = 8u * ((unsigned)cc + (unsigned)(l >> 4) * (unsigned)lds);
+      if (in) {
 #pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      const int row = (l >> 4) + 4 * j;
-      if (in && row < NC) dst[(int64_t)row * lds] = v[j];
+        for (int j = 0; j < 7; ++j) {
+          if (j < 6 || l < 16) {
+            char* bj = reinterpret_cast<char*>(st + (4 * i0 + 4 * j * lds));
+            asm("" : "+s"(bj));
+            *reinterpret_cast<s16_gdouble*>((s16_gchar*)bj + lo) = v[j];
+          }
+        }
+      }
+    } else {
+      double* dst = st + 4 * i0 + cc;
+      if (in) {
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+          const int row = (l >> 4) + 4 * j;
+          if (j < 6 || l < 16) dst[(int64_t)row * lds] = v[j];
+        }
+      }
     }
   }
 #ifdef RYD_S16_PROF
@@ -1151,16 +1250,30 @@ __device__ __forceinline__ void sym16_epilogue(double t, double z, double s00, d
     if (r == 13) v = (double)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));
     if (r == 14) v = s16_ts[7] - s16_ts[0];
 #endif
-    sm[(int64_t)r * ldm + i] = v;
-    if (r < 4) {
-      const double c = r == 0 ? (double)(NS * nuse) : r == 1 ? (double)(16 * nexec) : r == 2 ? tr11 : (double)nsq;
-      sm[(int64_t)(RYD_S_NMV_USEFUL + r) * ldm + i] = c;
-    }
-    if (r == 0) {
-      uint32_t stat = valid ? 0u : RYD_STATUS_BAD_INPUT;
-      if (over_cap) stat |= RYD_STATUS_STEP_CAP;
-      if (!fin) stat |= RYD_STATUS_NONFINITE;
-      status[i] = stat;
+    // the counters: one integer select, then one conversion (the same doubles)
+    const int ci = r == 0 ? NS * nuse : r == 1 ? 16 * nexec : nsq;
+    const double c = r == 2 ? tr11 : (double)ci;
+    uint32_t stat = valid ? 0u : RYD_STATUS_BAD_INPUT;
+    if (over_cap) stat |= RYD_STATUS_STEP_CAP;
+    if (!fin) stat |= RYD_STATUS_NONFINITE;
+    if (st32) {
+      // ip < n: the point is i0 + p.  Wave-uniform bases sm + i0, sm + 16 ldm + i0 and
+      // status + i0 plus the lane's 32-bit byte offsets (checked by launch())
+      char* b0 = reinterpret_cast<char*>(sm + i0);
+      char* b1 = reinterpret_cast<char*>(sm + (RYD_S_NMV_USEFUL * ldm + i0));
+      char* b2 = reinterpret_cast<char*>(status + i0);
+      asm("" : "+s"(b0));
+      asm("" : "+s"(b1));
+      asm("" : "+s"(b2));
+      const unsigned lo = 8u * ((unsigned)r * (unsigned)ldm + (unsigned)p);
+      *reinterpret_cast<s16_gdouble*>((s16_gchar*)b0 + lo) = v;
+      if (r < 4) *reinterpret_cast<s16_gdouble*>((s16_gchar*)b1 + lo) = c;
+      if (r == 0)
+        *reinterpret_cast<__attribute__((address_space(1))) uint32_t*>((s16_gchar*)b2 + 4u * (unsigned)p) = stat;
+    } else {
+      sm[(int64_t)r * ldm + i] = v;
+      if (r < 4) sm[(int64_t)(RYD_S_NMV_USEFUL + r) * ldm + i] = c;
+      if (r == 0) status[i] = stat;
     }
   }
 }
