@@ -147,7 +147,10 @@ extern "C" {
  *   RYD_C_K2              |00><11| -> coefficient of |00><11|
  *   RYD_C_K3              |01><10| -> coefficient of |01><10|
  * (no other qubit-block element is reachable from these inputs; the remaining
- * 6 units are the adjoints).                                                   */
+ * 6 units are the adjoints).  desc->dim 3 or 4: the rows mean the same in dim 4
+ * (the qubit block has the same support; RYD_P_GMJ_A/B add the mJ channel), where
+ * the qubit states |00>, |01>, |10>, |11> are indices 0, 1, 4, 5 of the
+ * 16-dimensional two-atom basis (0, 1, 3, 4 of the 9-dimensional one in dim 3). */
 #define RYD_C_K0   0
 #define RYD_C_K1   8
 #define RYD_C_K2  16

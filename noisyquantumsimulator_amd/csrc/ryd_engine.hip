@@ -2329,6 +2329,7 @@ __global__ __launch_bounds__(BLOCK) void coherence_cheb_kernel(const double* __r
 
 #include "ryd_coh_prop.inc"
 #include "ryd_dim4_prop.inc"
+#include "ryd_coh4_prop.inc"
 #include "ryd_shaped16.inc"
 
 // ---------------------------------------------------------------------------
@@ -2655,15 +2656,15 @@ bool coh_prop_enabled() {
   return !(e && e[0] == '0');
 }
 
-template <int PROTO>
+template <int PROTO, int DIM>
 int launch_coherences_proto(const double* dp, int64_t n, int64_t ldp, double* dc, int64_t ldc,
                             uint32_t* dstat, int ns, int sh, hipStream_t stream) {
   if (PROTO != RYD_PROTO_LP_SHAPED && coh_prop_enabled()) {   // one propagator per sector (ryd_coh_prop.inc)
     const int64_t blocks = (n + CP_NR - 1) / CP_NR;
     if (blocks > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
     void* args[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&dc, (void*)&ldc, (void*)&dstat, (void*)&ns, (void*)&sh};
-    HIPCHK(hipLaunchKernel((const void*)coherence_prop_kernel<PROTO>, dim3((unsigned)blocks), dim3(CP_BLOCK), args, 0,
-                           stream));
+    const void* k = DIM == 4 ? (const void*)coherence4_prop_kernel<PROTO> : (const void*)coherence_prop_kernel<PROTO>;
+    HIPCHK(hipLaunchKernel(k, dim3((unsigned)blocks), dim3(CP_BLOCK), args, 0, stream));
     return RYD_OK;
   }
   const int64_t nb2 = (2 * n + BLOCK - 1) / BLOCK, nb1 = (n + BLOCK - 1) / BLOCK;
@@ -2671,32 +2672,39 @@ int launch_coherences_proto(const double* dp, int64_t n, int64_t ldp, double* dc
   if (blocks > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
   void* args[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&dc, (void*)&ldc, (void*)&dstat,
                   (void*)&ns, (void*)&sh, (void*)&b0, (void*)&b1, (void*)&b2};
-  HIPCHK(hipLaunchKernel((const void*)coherence_cheb_kernel<PROTO>, dim3((unsigned)blocks), dim3(BLOCK), args, 0,
-                         stream));
+  const void* k = DIM == 4 ? (const void*)coherence4_cheb_kernel<PROTO> : (const void*)coherence_cheb_kernel<PROTO>;
+  HIPCHK(hipLaunchKernel(k, dim3((unsigned)blocks), dim3(BLOCK), args, 0, stream));
   return RYD_OK;
 }
 
+template <int DIM>
+int launch_coherences_dim(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, double* dc,
+                          int64_t ldc, uint32_t* dstat, hipStream_t stream) {
+  switch (d->protocol) {
+    case RYD_PROTO_LP_SQUARE:
+      return launch_coherences_proto<RYD_PROTO_LP_SQUARE, DIM>(dp, n, ldp, dc, ldc, dstat, d->n_steps, d->shape, stream);
+    case RYD_PROTO_LP_SHAPED:
+      return launch_coherences_proto<RYD_PROTO_LP_SHAPED, DIM>(dp, n, ldp, dc, ldc, dstat, d->n_steps, d->shape, stream);
+    case RYD_PROTO_BANGBANG:
+      return launch_coherences_proto<RYD_PROTO_BANGBANG, DIM>(dp, n, ldp, dc, ldc, dstat, d->n_steps, d->shape, stream);
+    default:
+      return launch_coherences_proto<RYD_PROTO_SMOOTH_JP, DIM>(dp, n, ldp, dc, ldc, dstat, d->n_steps, d->shape, stream);
+  }
+}
+
 // The coherence sectors of one batch (one launch); status is cleared first and each
-// sector ORs its bits in.
+// sector ORs its bits in.  dim 4: the kernels of ryd_coh4_prop.inc.
 int launch_coherences(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, double* dc,
                       int64_t ldc, uint32_t* dstat, hipStream_t stream) {
   if (n == 0) return RYD_OK;
   HIPCHK(hipMemsetAsync(dstat, 0, sizeof(uint32_t) * n, stream));
-  switch (d->protocol) {
-    case RYD_PROTO_LP_SQUARE:
-      return launch_coherences_proto<RYD_PROTO_LP_SQUARE>(dp, n, ldp, dc, ldc, dstat, d->n_steps, d->shape, stream);
-    case RYD_PROTO_LP_SHAPED:
-      return launch_coherences_proto<RYD_PROTO_LP_SHAPED>(dp, n, ldp, dc, ldc, dstat, d->n_steps, d->shape, stream);
-    case RYD_PROTO_BANGBANG:
-      return launch_coherences_proto<RYD_PROTO_BANGBANG>(dp, n, ldp, dc, ldc, dstat, d->n_steps, d->shape, stream);
-    default:
-      return launch_coherences_proto<RYD_PROTO_SMOOTH_JP>(dp, n, ldp, dc, ldc, dstat, d->n_steps, d->shape, stream);
-  }
+  return d->dim == 4 ? launch_coherences_dim<4>(d, dp, n, ldp, dc, ldc, dstat, stream)
+                     : launch_coherences_dim<3>(d, dp, n, ldp, dc, ldc, dstat, stream);
 }
 
 int validate_coherences(const ryd_batch_desc* d, int64_t n, int64_t ldp, int64_t ldc) {
   if (!d) return fail(RYD_ERR_INVALID, "desc is NULL");
-  if (d->dim != 3) return fail(RYD_ERR_UNSUPPORTED, "process-map coherences: dim 3 only");
+  if (d->dim != 3 && d->dim != 4) return fail(RYD_ERR_UNSUPPORTED, "process-map coherences: dim 3 or 4 only");
   ryd_batch_desc v = *d;                   // the Chebyshev vector method, Lindblad bookkeeping
   v.method = RYD_METHOD_CHEB_VECTOR;
   v.evolution = RYD_EVOL_LINDBLAD;

@@ -209,6 +209,15 @@ def symmetric_atoms(params: np.ndarray) -> bool:
                for k in ("G1", "G0", "GPHI", "GSC", "GMJ"))
 
 
+def check_coherence_dim(params: np.ndarray, dim: int) -> None:
+    """The process-map coherence kernels exist for dim 3 and 4; dim 3 has no mJ channel, so
+    a ``params`` with nonzero GMJ columns would have them silently ignored: refuse it."""
+    if dim not in (3, 4):
+        raise ValueError(f"process-map coherences: dim must be 3 or 4, not {dim}")
+    if dim == 3 and (np.any(params[N.P["GMJ_A"]] != 0) or np.any(params[N.P["GMJ_B"]] != 0)):
+        raise ValueError("params carry mJ leakage rates (GMJ_A / GMJ_B) that dim=3 would ignore; pass dim=4")
+
+
 def device_count() -> int:
     """GPUs visible to the HIP runtime (ryd_device_count)."""
     lib = N.load()
@@ -284,16 +293,18 @@ class Engine:
         return dict(pack_ms=buf[1], unpack_ms=buf[2], wall_ms=buf[3], slots=slots)
 
     def run_coherences(self, params: np.ndarray, protocol: str, n_steps: Optional[int] = None,
-                       shape: str = "square") -> Tuple[np.ndarray, np.ndarray]:
+                       shape: str = "square", dim: int = 3) -> Tuple[np.ndarray, np.ndarray]:
         """The 6 upper off-diagonal qubit matrix units through the gate
-        (ryd_run_coherences): returns (coh (NCOH, n) float64, status (n,) uint32)."""
+        (ryd_run_coherences): returns (coh (NCOH, n) float64, status (n,) uint32).  The rows
+        mean the same for ``dim`` 3 and 4 (the qubit block has the same support)."""
         params = np.ascontiguousarray(params, dtype=np.float64)
         if params.shape[0] != N.NPARAM:
             raise ValueError(f"params must have shape ({N.NPARAM}, n)")
+        check_coherence_dim(params, dim)
         n = params.shape[1]
         if n_steps is None:
             n_steps = default_n_steps(protocol, params)
-        desc = make_desc(protocol, "lindblad", n_steps, shape, symmetric_atoms(params), "cheb_vector")
+        desc = make_desc(protocol, "lindblad", n_steps, shape, symmetric_atoms(params), "cheb_vector", dim=dim)
         coh = np.zeros((N.NCOH, n), dtype=np.float64)
         status = np.zeros(n, dtype=np.uint32)
         st = N.Stats()
@@ -520,18 +531,21 @@ class DeviceSweep:
 
 
 class CoherenceDeviceBatch:
-    """Process-map coherence sectors (ryd_run_coherences_device: the four
-    coherence_cheb_kernel launches) with inputs resident in HBM, for timed re-runs."""
+    """Process-map coherence sectors (ryd_run_coherences_device: one launch of the dim-3 or
+    dim-4 coherence kernel) with inputs resident in HBM, for timed re-runs."""
 
     def __init__(self, engine: Engine, params: np.ndarray, protocol: str, n_steps: Optional[int] = None,
-                 shape: str = "square", slot: int = 0):
+                 shape: str = "square", slot: int = 0, dim: int = 3):
         self.eng, self.slot = engine, slot
         lib = engine.lib
         params = np.ascontiguousarray(params, dtype=np.float64)
+        check_coherence_dim(params, dim)
+        self.dim = dim
         self.n = n = params.shape[1]
         if n_steps is None:
             n_steps = default_n_steps(protocol, params)
-        self.desc = make_desc(protocol, "lindblad", n_steps, shape, symmetric_atoms(params), "cheb_vector")
+        self.desc = make_desc(protocol, "lindblad", n_steps, shape, symmetric_atoms(params), "cheb_vector",
+                              dim=dim)
         self._bufs = []
 
         def alloc(nbytes):

@@ -6,7 +6,7 @@ but ships only a stub (src/qpu_simulator/noise_models/__init__.py:1-22).  Here
 it sits on the GPU engine:
 
 * the 4 diagonal qubit inputs |x><x| come from the Lindblad state of
-  ``ryd_run_batch`` (the real 25-dim sector);
+  ``ryd_run_batch`` (the real 25-dim sector; 36-dim for hilbert_space_dim 4);
 * the 6 upper off-diagonal qubit matrix units come from ``ryd_run_coherences``
   (each evolved in its own excitation-number sector, see the kernel comment in
   csrc/ryd_engine.hip); the other 6 are adjoints.
@@ -39,16 +39,19 @@ PAULI2 = np.array([np.kron(P, Q) for P in _P1 for Q in _P1])          # (16, 4, 
 _CHI = np.array([[1.0 if np.allclose(Pi @ Pj, Pj @ Pi) else -1.0 for Pj in PAULI2] for Pi in PAULI2])
 
 
-def assemble_maps(state: np.ndarray, coh: np.ndarray) -> np.ndarray:
-    """S (n, 16, 16) complex from the Lindblad state rows (25, 4n) of the diagonal
-    inputs and the coherence rows (NCOH, n)."""
+def assemble_maps(state: np.ndarray, coh: np.ndarray, dim: int = 3) -> np.ndarray:
+    """S (n, 16, 16) complex from the Lindblad state rows (25, 4n) -- (36, 4n) for
+    ``dim`` 4 -- of the diagonal inputs and the coherence rows (NCOH, n)."""
+    if dim not in (3, 4):
+        raise ValueError(f"assemble_maps: dim must be 3 or 4, not {dim}")
     n = coh.shape[1]
-    R = state.reshape(25, n, 4)                                     # [e_A*5 + e_B][point][input x]
+    ne = 5 if dim == 3 else 6                                       # single-atom sector basis size
+    R = state.reshape(ne * ne, n, 4)                                # [e_A*ne + e_B][point][input x]
     S = np.zeros((n, 16, 16), dtype=complex)
     for x in range(4):
         for y in range(4):                                          # <y|E(|x><x|)|y>
             ya, yb = QUBIT_E[y >> 1], QUBIT_E[y & 1]
-            S[:, 5 * y, 5 * x] = R[5 * ya + yb, :, x]
+            S[:, 5 * y, 5 * x] = R[ne * ya + yb, :, x]
     c = lambda row: coh[row] + 1j * coh[row + 1]
     pairs = ((N.C["K0"], ((0, 1), (2, 3))),     # inputs |00><01|, |10><11| ; outputs the same pair
              (N.C["K1"], ((0, 2), (1, 3))))     # inputs |00><10|, |01><11|
@@ -187,11 +190,14 @@ def analyse(S: np.ndarray, status: Optional[np.ndarray] = None, with_kraus: bool
 
 
 def gate_process_maps(params: np.ndarray, protocol: str, n_steps: Optional[int] = None,
-                      shape: str = "square", engine=None, with_kraus: bool = False) -> ProcessMaps:
-    """Process maps of a batch of packed points (engine.pack_params layout) on the GPU."""
+                      shape: str = "square", engine=None, with_kraus: bool = False,
+                      dim: int = 3) -> ProcessMaps:
+    """Process maps of a batch of packed points (engine.pack_params layout) on the GPU;
+    ``dim`` 4 includes the mJ channel (GMJ columns), which ``dim`` 3 refuses to drop."""
     from . import engine as E
     eng = engine if engine is not None else E.Engine()
-    diag = eng.run(params, protocol, "lindblad", n_steps=n_steps, shape=shape)
-    coh, cst = eng.run_coherences(params, protocol, n_steps=n_steps, shape=shape)
-    S = assemble_maps(diag.state, coh)
+    E.check_coherence_dim(np.asarray(params), dim)
+    diag = eng.run(params, protocol, "lindblad", n_steps=n_steps, shape=shape, dim=dim)
+    coh, cst = eng.run_coherences(params, protocol, n_steps=n_steps, shape=shape, dim=dim)
+    S = assemble_maps(diag.state, coh, dim)
     return analyse(S, diag.status | cst, with_kraus=with_kraus)

@@ -297,8 +297,8 @@ class BatchResult:
     is_mixed: np.ndarray
     states: Optional[np.ndarray] = None   # rho (n,4,9,9) or kets (n,4,9) (complex)
     kernel_ms: float = 0.0
-    # gauge-invariant figures of merit (``process_fidelity=True``; NaN otherwise, and for
-    # dim 4 Lindblad points): process / average gate fidelity to CZ up to local Z phases
+    # gauge-invariant figures of merit (``process_fidelity=True``; NaN otherwise): process /
+    # average gate fidelity to CZ up to local Z phases
     process_fidelity: Optional[np.ndarray] = None
     avg_gate_fidelity: Optional[np.ndarray] = None
     timings: Dict[str, float] = field(default_factory=dict)   # host wall ms per stage
@@ -441,7 +441,7 @@ def simulate_CZ_gate_batch(simulation_inputs, n: Optional[int] = None, *, specie
     ``process_fidelity``: also compute the gauge-invariant process fidelity and average
     gate fidelity to CZ up to local Z phases (noise_models.gate_fidelity) -- from the
     kets for noise-free points, from the Lindblad state plus one ryd_run_coherences pass
-    (the 6 qubit coherences) for noisy dim-3 points."""
+    (the 6 qubit coherences) for noisy points, in dim 3 and dim 4 (shaped LP included)."""
     if hilbert_space_dim not in (3, 4):
         raise ValueError(f"Unsupported Hilbert space dimension: {hilbert_space_dim}. Use 3 or 4.")
     dim = hilbert_space_dim
@@ -518,13 +518,13 @@ def simulate_CZ_gate_batch(simulation_inputs, n: Optional[int] = None, *, specie
                 prm = E.pack_params(b, loc)
                 r = eng.run(prm, key, evol, shape=shape, method=method if dim == 3 else "chebyshev", dim=dim)
                 coh = None
-                if process_fidelity and evol == "lindblad" and dim == 3:
-                    coh, cst = eng.run_coherences(prm, key, shape=shape)
+                if process_fidelity and evol == "lindblad":
+                    coh, cst = eng.run_coherences(prm, key, shape=shape, dim=dim)
                     status[idx] |= cst
                 engine_s += time.perf_counter() - t0
                 if process_fidelity and (evol == "ket" or coh is not None):
                     from . import noise_models as NM
-                    S = NM.ket_maps(r.kets(), dim) if evol == "ket" else NM.assemble_maps(r.state, coh)
+                    S = NM.ket_maps(r.kets(), dim) if evol == "ket" else NM.assemble_maps(r.state, coh, dim)
                     fpro[idx], fgate[idx] = NM.gate_fidelity(S)
                 kms += r.kernel_ms
                 status[idx] |= r.status
@@ -615,7 +615,7 @@ def simulate_CZ_gate(
 ) -> Union[SimulationResult, Dict]:
     """Drop-in for RG/simulation.py:2534 (same arguments, same outputs) on the GPU engine.
     ``process_fidelity=True`` also fills the gauge-invariant ``process_fidelity`` and
-    ``avg_gate_fidelity`` (dim 3; noise-free points in dim 4)."""
+    ``avg_gate_fidelity`` (dim 3 and dim 4, noisy or noise-free)."""
     if config is None:
         config = AtomicConfiguration(species=species, qubit_0=qubit_0, qubit_1=qubit_1,
                                      n_rydberg=n_rydberg, L_rydberg="S")
