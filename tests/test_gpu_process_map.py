@@ -33,6 +33,24 @@ def test_process_map_matches_oracle(eng, protocol, n_steps):
     assert np.all(pm.kraus_rank > 1)                      # noisy: not a unitary channel
 
 
+@pytest.mark.parametrize("protocol,n_steps", [("lp_square", None), ("smooth_jp", 30), ("bangbang", None)])
+def test_process_map_identical_atoms_matches_oracle(eng, protocol, n_steps):
+    """B rates = A rates: coherence_prop_kernel mirrors the (-1, 0) sector from (0, -1) instead
+    of building it -- the path of every reference configuration and of the bench."""
+    rng = np.random.default_rng(101)
+    p = _random_points(rng, 5, protocol)
+    for k in ("G1", "G0", "GPHI", "GSC"):
+        p[N.P[k + "_B"]] = p[N.P[k + "_A"]]
+    assert E.symmetric_atoms(p)
+    pm = NM.gate_process_maps(p, protocol, n_steps=n_steps, engine=eng, with_kraus=True)
+    assert np.all(pm.status == 0)
+    for i in range(5):
+        ref = O.process_map(spec_from_params(p, i, protocol, n_steps=n_steps or 300))
+        print(f"{protocol} identical atoms, point {i}: max|dS| = {np.abs(pm.S[i] - ref).max():.3e}")
+        np.testing.assert_allclose(pm.S[i], ref, atol=TOL, rtol=0)
+    assert np.all(pm.kraus_rank > 1)
+
+
 def test_noise_free_map_is_the_ket_unitary(eng):
     """Zero rates: the coherence kernels and the ket kernel are independent routes to
     the same qubit-block unitary, S = U_q (x) conj(U_q)."""
