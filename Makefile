@@ -25,7 +25,12 @@ asm: $(SRC)
 check-dpp: asm
 	python3 tools/check_dpp_hazards.py $(ASM)
 
+# the gfx950 code of another build (BASE=<its libryd_engine.so>) against this one, kernel by
+# kernel: identical disassembly or not, registers / scratch / LDS, instruction-class histograms
+kernel-diff: $(SO)
+	python3 tools/kernel_diff.py $(BASE) $(SO)
+
 clean:
 	rm -f $(SO)
 
-.PHONY: all clean resource-usage asm check-dpp
+.PHONY: all clean resource-usage asm check-dpp kernel-diff

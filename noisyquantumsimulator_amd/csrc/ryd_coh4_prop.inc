@@ -16,11 +16,13 @@
 // The output rows RYD_C_* are the dim-3 ones (the qubit block has the same support).
 //
 // coherence4_cheb_kernel: one lane per (point, input) and sector, a Chebyshev series per
-// segment (LP shaped; RYD_COH_PROP=0).  coherence4_prop_kernel: coherence_prop_kernel's
-// mapping -- one 16-lane DPP row per point, lane c < 12 builds column c of the (0,-1)
-// phase-0 propagator, squarings in registers (the 2 columns with the q = 0 atom in |0><0|
-// feed only themselves: 124 complex products instead of 144), the quad sectors on quads 0
-// and 1 of the same row.
+// segment (LP shaped; RYD_COH_PROP=0): coherence_cheb_body (ryd_engine.hip) on Sector4, the
+// description below, which also serves lindblad4_cheb_kernel.  coherence4_prop_kernel:
+// coherence_prop_kernel's mapping -- one 16-lane DPP row per point, lane c < 12 builds column
+// c of the (0,-1) phase-0 propagator, squarings in registers (the 2 columns with the q = 0
+// atom in |0><0| feed only themselves: 124 complex products instead of 144), the quad sectors
+// on quads 0 and 1 of the same row.  c4_sector repeats cp_sector's control flow (see DESIGN.md
+// section 0 for why the two are not one body).
 
 constexpr int C4_NMAX = 12;
 
@@ -29,10 +31,6 @@ __device__ __forceinline__ CGen make_cgen4(const Seg& g, double d1, const double
   CGen c = make_cgen(g, d1, r, s, conj);
   c.m11r = -0.5 * s * (r[0] + r[1] + r[2] + gm);
   return c;
-}
-
-__device__ __forceinline__ bool gmj_valid(double gmA, double gmB) {
-  return gmA >= 0.0 && gmB >= 0.0 && isfinite(gmA) && isfinite(gmB);
 }
 
 // o[0..5] += M u[0..5] (apply4_one's rows) for one (re or im) component, stride-addressed.
@@ -96,79 +94,69 @@ __device__ __forceinline__ void apply4_coh(const Gen4& Q0, const CGen& Qm, doubl
   }
 }
 
-// ---- the per-lane Chebyshev kernel (coherence_sector for dim 4) ------------------------
-template <int PROTO, int KIND>
-__device__ __forceinline__ void coherence4_sector(const double* __restrict__ prm, int64_t n, int64_t ldp,
-                                                  double* __restrict__ out, int64_t ldo,
-                                                  uint32_t* __restrict__ status, int n_steps, int shape,
-                                                  int64_t blk) {
-  constexpr int NIN = KIND < 2 ? 2 : 1;
-  constexpr int NV = KIND < 2 ? 24 : 8;
-  const int64_t gid = blk * BLOCK + threadIdx.x;
-  const bool live = gid < NIN * n;
-  const int64_t i = live ? gid / NIN : (n - 1);
-  const int sub = (int)(gid % NIN);
-  const PointP q = load_point<PROTO>(prm, ldp, i);
-  const double gmA = col(prm, RYD_P_GMJ_A, ldp, i), gmB = col(prm, RYD_P_GMJ_B, ldp, i);
-  const bool valid = point_valid<PROTO>(q, n_steps) && gmj_valid(gmA, gmB);
-  // start: KIND 0 C[sub][0], KIND 1 C[0][sub], KIND 2/3 C[0][0]
-  const int e0 = KIND == 0 ? 4 * sub : (KIND == 1 ? 2 * sub : 0);
-  double v[NV];
-#pragma unroll
-  for (int e = 0; e < NV; ++e) v[e] = (e == e0) ? 1.0 : 0.0;
-  double nuse = 0.0, nexec = 0.0;
-  bool over_cap = false;
-  const int nseg = n_segments<PROTO>(n_steps);
-  double rsum = 2.0 * (fabs(gmA) + fabs(gmB));
-#pragma unroll
-  for (int c = 0; c < 4; ++c) rsum += fabs(q.gA[c]) + fabs(q.gB[c]);
-  for (int s = 0; s < nseg; ++s) {
-    const Seg g = segment<PROTO>(q, s, n_steps, shape);
-    double emin, emax;
-    h_bounds(g, q.V, q.d1, emin, emax);
-    const double omega = (emax - emin) + rsum;
-    const double x = omega * g.dt;
-    const bool capped = valid && !(x <= X_CAP);
-    const bool active = valid && !capped && x > X_SKIP;
-    over_cap = over_cap || capped;
-    const double sc = active ? 2.0 / omega : 0.0;
-    const double vs = sc * 0.5 * q.V;
-    if constexpr (KIND < 2) {
-      const Gen4 Q0 = KIND == 0 ? make_gen4(g, q.d1, q.gA, gmA, sc) : make_gen4(g, q.d1, q.gB, gmB, sc);
-      const CGen Qm = KIND == 0 ? make_cgen4(g, q.d1, q.gB, gmB, sc, false)
-                                : make_cgen4(g, q.d1, q.gA, gmA, sc, false);
-      cheb_segment<NV>(v, x, active,
-                       [&](const double (&b)[NV], double (&o)[NV]) { apply4_coh<KIND, false>(Q0, Qm, vs, b, o); },
-                       nuse, nexec);
-    } else {
-      const Gen Z = {};
-      const CGen Am = make_cgen4(g, q.d1, q.gA, gmA, sc, false);
-      const CGen Bm = make_cgen4(g, q.d1, q.gB, gmB, sc, KIND == 3);
-      cheb_segment<NV>(v, x, active,
-                       [&](const double (&b)[NV], double (&o)[NV]) { apply_coh<KIND>(Z, Z, Am, Bm, vs, b, o); },
-                       nuse, nexec);
-    }
+// ---- hilbert_space_dim = 4 for the per-lane Chebyshev bodies (ryd_engine.hip) -----------
+// Per-atom q = 0 block {e00, e11, e++, ex, ey, e--}, q = -1 block {|0><1|, |0><r+|}, the mJ
+// mixing rates GMJ_A / GMJ_B as extra parameter columns.
+struct Sector4 {
+  static constexpr int NB = 6;                 // q = 0 block of one atom
+  static constexpr int NS = NB * NB;           // the real (0,0) sector (state vector)
+  static constexpr int NROW = 2 * NB;          // complex coordinates of a row sector
+  struct Mj {                                  // the extra parameter columns
+    double a, b;
+  };
+  __device__ static __forceinline__ Mj load_mj(const double* prm, int64_t ldp, int64_t i) {
+    return {col(prm, RYD_P_GMJ_A, ldp, i), col(prm, RYD_P_GMJ_B, ldp, i)};
   }
-  uint32_t stat = valid ? 0u : RYD_STATUS_BAD_INPUT;
-  if (over_cap) stat |= RYD_STATUS_STEP_CAP;
-  if (!finite_all(v, NV)) stat |= RYD_STATUS_NONFINITE;
-  if (!live) return;
-  if (KIND < 2) {
-    const int base = (KIND == 0 ? RYD_C_K0 : RYD_C_K1) + 4 * sub;
-    const int i1 = KIND == 0 ? 4 : 2;
-    out[(int64_t)(base + 0) * ldo + i] = v[0];
-    out[(int64_t)(base + 1) * ldo + i] = v[1];
-    out[(int64_t)(base + 2) * ldo + i] = v[i1];
-    out[(int64_t)(base + 3) * ldo + i] = v[i1 + 1];
-  } else {
-    const int base = KIND == 2 ? RYD_C_K2 : RYD_C_K3;
-    out[(int64_t)(base + 0) * ldo + i] = v[0];
-    out[(int64_t)(base + 1) * ldo + i] = v[1];
+  __device__ static __forceinline__ bool mj_valid(const Mj& m) { return gmj_valid(m.a, m.b); }
+  __device__ static __forceinline__ bool mj_valid(bool ok, const Mj& m) { return gmj_valid(ok, m.a, m.b); }
+  __device__ static __forceinline__ double rate_extra(const Mj& m) {           // their term of the rate sum
+    return 2.0 * (fabs(m.a) + fabs(m.b));
   }
-  if (stat) atomicOr(&status[i], stat);
-  (void)nuse;
-  (void)nexec;
-}
+  __host__ __device__ static constexpr bool population(int a) { return a < 3 || a == 5; }   // e00, e11, e++, e--
+
+  struct StateGen {
+    Gen4 A, B;
+  };
+  // SYM (identical atoms): B is A
+  template <bool SYM>
+  __device__ static __forceinline__ StateGen state_gen(const Seg& g, const PointP& q, const Mj& m, double sc) {
+    const Gen4 A = make_gen4(g, q.d1, q.gA, m.a, sc);
+    return {A, SYM ? A : make_gen4(g, q.d1, q.gB, m.b, sc)};
+  }
+  template <bool SYM>
+  __device__ static __forceinline__ void state_apply(const StateGen& G, double vs, const double (&b)[NS],
+                                                     double (&o)[NS]) {
+    apply4_one<6>(G.A, b, o);
+    apply4_one<1>(G.B, b, o);
+    apply4_V(vs, b, o);
+  }
+
+  // sector KIND's generator blocks: a row sector reads Q0 (the q = 0 atom: A for KIND 0, B for
+  // KIND 1) and Qm (the other atom's q = -1 block), the quads Am and Bm (B's block conjugated
+  // for KIND 3, the (-1,+1) sector)
+  struct RowGen {
+    Gen4 Q0;
+    CGen Qm;
+  };
+  struct QuadGen {
+    CGen Am, Bm;
+  };
+  template <int KIND>
+  __device__ static __forceinline__ auto coh_gen(const Seg& g, const PointP& q, const Mj& m, double sc) {
+    if constexpr (KIND == 0)
+      return RowGen{make_gen4(g, q.d1, q.gA, m.a, sc), make_cgen4(g, q.d1, q.gB, m.b, sc, false)};
+    else if constexpr (KIND == 1)
+      return RowGen{make_gen4(g, q.d1, q.gB, m.b, sc), make_cgen4(g, q.d1, q.gA, m.a, sc, false)};
+    else
+      return QuadGen{make_cgen4(g, q.d1, q.gA, m.a, sc, false), make_cgen4(g, q.d1, q.gB, m.b, sc, KIND == 3)};
+  }
+  // the quads have no q = 0 factor: dim 3's apply with those blocks zero
+  template <int KIND, typename G>
+  __device__ static __forceinline__ void coh_apply(const G& c, double vs, const double* b, double* o) {
+    if constexpr (KIND < 2) apply4_coh<KIND, false>(c.Q0, c.Qm, vs, b, o);
+    else apply_coh<KIND>(Gen{}, Gen{}, c.Am, c.Bm, vs, b, o);
+  }
+};
 
 // the four sectors in one launch, as coherence_cheb_kernel
 template <int PROTO>
@@ -176,11 +164,7 @@ __global__ __launch_bounds__(BLOCK) void coherence4_cheb_kernel(const double* __
                                                                 int64_t ldp, double* __restrict__ out, int64_t ldo,
                                                                 uint32_t* __restrict__ status, int n_steps,
                                                                 int shape, int64_t b0, int64_t b1, int64_t b2) {
-  const int64_t b = blockIdx.x;
-  if (b < b0) coherence4_sector<PROTO, 0>(prm, n, ldp, out, ldo, status, n_steps, shape, b);
-  else if (b < b1) coherence4_sector<PROTO, 1>(prm, n, ldp, out, ldo, status, n_steps, shape, b - b0);
-  else if (b < b2) coherence4_sector<PROTO, 2>(prm, n, ldp, out, ldo, status, n_steps, shape, b - b1);
-  else coherence4_sector<PROTO, 3>(prm, n, ldp, out, ldo, status, n_steps, shape, b - b2);
+  coherence_cheb_body<PROTO, Sector4>(prm, n, ldp, out, ldo, status, n_steps, shape, b0, b1, b2);
 }
 
 // ---- the propagator kernel -------------------------------------------------------------

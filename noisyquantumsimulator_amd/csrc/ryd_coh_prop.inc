@@ -602,9 +602,7 @@ __global__ __launch_bounds__(CP_BLOCK) __attribute__((amdgpu_waves_per_eu(RYD_CP
   // (-1,0) is the atom-swap mirror of (0,-1) when the atoms are identical (the images are
   // the same numbers); otherwise it is built
   cp_sector<PROTO, 0>(prm, ldp, valid, n_steps, shape, l, Ul, stg, zl, out, ldo, i, live, sym, stat);
-#ifndef RYD_CP_PROBE_NOK2                         // (timing probe: the quad sectors left out)
   cp_sector<PROTO, 2>(prm, ldp, valid, n_steps, shape, l, Ul, stg, zl, out, ldo, i, live, false, stat);
-#endif
   if (__ballot(!sym && live)) cp_sector<PROTO, 1>(prm, ldp, valid, n_steps, shape, l, Ul, stg, zl, out, ldo, i, live && !sym, false, stat);
   // the row's flags (every lane of the wave reaches this)
   uint32_t st = stat;

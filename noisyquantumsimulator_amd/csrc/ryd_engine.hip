@@ -521,64 +521,98 @@ __device__ __forceinline__ bool point_valid(const PointP& q, int n_steps) {
   return ok;
 }
 
+__device__ __forceinline__ bool gmj_valid(double gmA, double gmB) {
+  return gmA >= 0.0 && gmB >= 0.0 && isfinite(gmA) && isfinite(gmB);
+}
+// ok && gmj_valid(gmA, gmB) as one chain of tests.  The compiler turns the two spellings into
+// different compare sequences, so each kernel keeps the one it was measured with: the state
+// kernels the chain, the coherence kernels the nested form.
+__device__ __forceinline__ bool gmj_valid(bool ok, double gmA, double gmB) {
+  return ok && gmA >= 0.0 && gmB >= 0.0 && isfinite(gmA) && isfinite(gmB);
+}
+
+// The Chebyshev scaling of one segment in the per-lane kernels: the generator's spectrum lies
+// within omega = (Gershgorin width of H) + rsum (the rate sum), x = omega dt is the series
+// argument, sc the generator's scale (0 on a lane that sits the segment out).
+struct SegScale {
+  double x;
+  bool active, capped;
+  double sc;
+};
+__device__ __forceinline__ SegScale seg_scale(const Seg& g, double V, double d1, double rsum, bool valid) {
+  double emin, emax;
+  h_bounds(g, V, d1, emin, emax);
+  const double omega = (emax - emin) + rsum;
+  const double x = omega * g.dt;
+  const bool capped = valid && !(x <= X_CAP);
+  const bool active = valid && !capped && x > X_SKIP;
+  return {x, active, capped, active ? 2.0 / omega : 0.0};
+}
+
+// What differs between hilbert_space_dim = 3 and 4 in the per-lane Chebyshev kernels (states
+// and coherences): sizes, the extra parameter columns, generators, the trace mask.  Sector3 is
+// defined below (before coherence_sector), Sector4 in ryd_coh4_prop.inc, each after the helpers
+// it names; the kernels that name them are templates, instantiated after both.  The bodies
+// templated on them reach everything dimension-specific through their members.
+struct Sector3;
+struct Sector4;
+
 // Epilogue shared by both evolutions: gather the 4 lanes of a point.
 __device__ __forceinline__ double lane_get(double v, int src) { return __shfl(v, src, 64); }
 
-template <int PROTO, bool SYM>
-__global__ __launch_bounds__(BLOCK) void lindblad_cheb_kernel(
+// One lane per (point, basis input): the S::NS-vector of the real (0,0) sector through every
+// segment by cheb_segment, then the populations, the trace of the |11> input and the summary.
+template <int PROTO, bool SYM, typename S>
+__device__ __forceinline__ void lindblad_cheb_body(
     const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st, int64_t lds,
     double* __restrict__ sm, int64_t ldm, uint32_t* __restrict__ status, int n_steps, int shape) {
+  constexpr int NB = S::NB, NS = S::NS;
   const int64_t gid = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
   const bool live = gid < 4 * n;
   const int64_t i = live ? (gid >> 2) : (n - 1);
   const int inp = (int)(gid & 3);
   const int a1 = inp >> 1, a2 = inp & 1;
   const PointP q = load_point<PROTO>(prm, ldp, i);
-  const bool valid = point_valid<PROTO>(q, n_steps);
+  const typename S::Mj mj = S::load_mj(prm, ldp, i);
+  const bool valid = S::mj_valid(point_valid<PROTO>(q, n_steps), mj);
 
-  const int e0 = 5 * a1 + a2;     // |a1 a2><a1 a2| = e_{a1} (x) e_{a2}
-  double v[25];
+  const int e0 = NB * a1 + a2;     // |a1 a2><a1 a2| = e_{a1} (x) e_{a2}
+  double v[NS];
 #pragma unroll
-  for (int e = 0; e < 25; ++e) v[e] = (e == e0) ? 1.0 : 0.0;   // static indices: stays in VGPRs
+  for (int e = 0; e < NS; ++e) v[e] = (e == e0) ? 1.0 : 0.0;   // static indices: stays in VGPRs
   double nuse = 0.0, nexec = 0.0;
   bool over_cap = false;
   const int nseg = n_segments<PROTO>(n_steps);
-  double rsum = 0.0;
+  double rsum = S::rate_extra(mj);
 #pragma unroll
   for (int c = 0; c < 4; ++c) rsum += fabs(q.gA[c]) + fabs(q.gB[c]);
   for (int s = 0; s < nseg; ++s) {
     const Seg g = segment<PROTO>(q, s, n_steps, shape);
-    double emin, emax;
-    h_bounds(g, q.V, q.d1, emin, emax);
-    const double omega = (emax - emin) + rsum;
-    const double x = omega * g.dt;
-    const bool capped = valid && !(x <= X_CAP);
-    const bool active = valid && !capped && x > X_SKIP;
-    over_cap = over_cap || capped;
-    const double sc = active ? 2.0 / omega : 0.0;
-    const Gen A = make_gen(g, q.d1, q.gA, sc);
-    const Gen B = make_gen(g, q.d1, q.gB, sc);
-    const double vs = sc * 0.5 * q.V;
-    cheb_segment<25>(v, x, active,
-                     [&](const double (&b)[25], double (&o)[25]) { apply_L<SYM>(A, B, vs, b, o); },
+    const SegScale k = seg_scale(g, q.V, q.d1, rsum, valid);
+    over_cap = over_cap || k.capped;
+    const auto G = S::template state_gen<SYM>(g, q, mj, k.sc);
+    const double vs = k.sc * 0.5 * q.V;
+    cheb_segment<NS>(v, k.x, k.active,
+                     [&](const double (&b)[NS], double (&o)[NS]) { S::template state_apply<SYM>(G, vs, b, o); },
                      nuse, nexec);
   }
 
   // epilogue
   double pop = 0.0;
 #pragma unroll
-  for (int e = 0; e < 25; ++e) pop = (e == e0) ? v[e] : pop;
-  double tr = 0.0;
+  for (int e = 0; e < NS; ++e) pop = (e == e0) ? v[e] : pop;
+  double tr = 0.0;                 // trace: the population coordinates of both atoms
 #pragma unroll
-  for (int ii = 0; ii < 3; ++ii)
+  for (int ii = 0; ii < NB; ++ii)
 #pragma unroll
-    for (int jj = 0; jj < 3; ++jj) tr += v[5 * ii + jj];
+    for (int jj = 0; jj < NB; ++jj)
+      if (S::population(ii) && S::population(jj)) tr += v[NB * ii + jj];
   uint32_t stat = valid ? 0u : RYD_STATUS_BAD_INPUT;
   if (over_cap) stat |= RYD_STATUS_STEP_CAP;
-  if (!finite_all(v, 25)) stat |= RYD_STATUS_NONFINITE;
+  if (!finite_all(v, NS)) stat |= RYD_STATUS_NONFINITE;
   if (live) {
 #pragma unroll
-    for (int e = 0; e < 25; ++e) st[(int64_t)e * lds + gid] = v[e];
+    for (int e = 0; e < NS; ++e) st[(int64_t)e * lds + gid] = v[e];
   }
   const int lane = threadIdx.x & 63, base = lane & ~3;
   double p[4];
@@ -607,6 +641,13 @@ __global__ __launch_bounds__(BLOCK) void lindblad_cheb_kernel(
     sm[(int64_t)RYD_S_NSQUARE * ldm + i] = 0.0;
     status[i] = st_all;
   }
+}
+
+template <int PROTO, bool SYM>
+__global__ __launch_bounds__(BLOCK) void lindblad_cheb_kernel(
+    const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st, int64_t lds,
+    double* __restrict__ sm, int64_t ldm, uint32_t* __restrict__ status, int n_steps, int shape) {
+  lindblad_cheb_body<PROTO, SYM, Sector3>(prm, n, ldp, st, lds, sm, ldm, status, n_steps, shape);
 }
 
 template <int PROTO, int KD>
@@ -1087,89 +1128,7 @@ template <int PROTO, bool SYM>
 __global__ __launch_bounds__(BLOCK) void lindblad4_cheb_kernel(
     const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st, int64_t lds,
     double* __restrict__ sm, int64_t ldm, uint32_t* __restrict__ status, int n_steps, int shape) {
-  const int64_t gid = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  const bool live = gid < 4 * n;
-  const int64_t i = live ? (gid >> 2) : (n - 1);
-  const int inp = (int)(gid & 3);
-  const int a1 = inp >> 1, a2 = inp & 1;
-  const PointP q = load_point<PROTO>(prm, ldp, i);
-  const double gmA = col(prm, RYD_P_GMJ_A, ldp, i), gmB = col(prm, RYD_P_GMJ_B, ldp, i);
-  const bool valid = point_valid<PROTO>(q, n_steps) && gmA >= 0.0 && gmB >= 0.0 && isfinite(gmA) &&
-                     isfinite(gmB);
-  const int e0 = 6 * a1 + a2;
-  double v[36];
-#pragma unroll
-  for (int e = 0; e < 36; ++e) v[e] = (e == e0) ? 1.0 : 0.0;
-  double nuse = 0.0, nexec = 0.0;
-  bool over_cap = false;
-  const int nseg = n_segments<PROTO>(n_steps);
-  double rsum = 2.0 * (fabs(gmA) + fabs(gmB));
-#pragma unroll
-  for (int c = 0; c < 4; ++c) rsum += fabs(q.gA[c]) + fabs(q.gB[c]);
-  for (int s = 0; s < nseg; ++s) {
-    const Seg g = segment<PROTO>(q, s, n_steps, shape);
-    double emin, emax;
-    h_bounds(g, q.V, q.d1, emin, emax);
-    const double omega = (emax - emin) + rsum;
-    const double x = omega * g.dt;
-    const bool capped = valid && !(x <= X_CAP);
-    const bool active = valid && !capped && x > X_SKIP;
-    over_cap = over_cap || capped;
-    const double sc = active ? 2.0 / omega : 0.0;
-    const Gen4 A = make_gen4(g, q.d1, q.gA, gmA, sc);
-    const Gen4 B = SYM ? A : make_gen4(g, q.d1, q.gB, gmB, sc);
-    const double vs = sc * 0.5 * q.V;
-    cheb_segment<36>(v, x, active,
-                     [&](const double (&b)[36], double (&o)[36]) {
-                       apply4_one<6>(A, b, o);
-                       apply4_one<1>(B, b, o);
-                       apply4_V(vs, b, o);
-                     },
-                     nuse, nexec);
-  }
-  double pop = 0.0;
-#pragma unroll
-  for (int e = 0; e < 36; ++e) pop = (e == e0) ? v[e] : pop;
-  double tr = 0.0;                         // trace: population coordinates {0,1,2,5} x {0,1,2,5}
-#pragma unroll
-  for (int ii = 0; ii < 6; ++ii)
-#pragma unroll
-    for (int jj = 0; jj < 6; ++jj)
-      if ((ii < 3 || ii == 5) && (jj < 3 || jj == 5)) tr += v[6 * ii + jj];
-  uint32_t stat = valid ? 0u : RYD_STATUS_BAD_INPUT;
-  if (over_cap) stat |= RYD_STATUS_STEP_CAP;
-  if (!finite_all(v, 36)) stat |= RYD_STATUS_NONFINITE;
-  if (live) {
-#pragma unroll
-    for (int e = 0; e < 36; ++e) st[(int64_t)e * lds + gid] = v[e];
-  }
-  const int lane = threadIdx.x & 63, base = lane & ~3;
-  double p[4];
-#pragma unroll
-  for (int x = 0; x < 4; ++x) p[x] = lane_get(pop, base + x);
-  const double tr11 = lane_get(tr, base + 3);
-  uint32_t st_all = stat;
-#pragma unroll
-  for (int x = 1; x < 4; ++x) st_all |= (uint32_t)__shfl((int)stat, base + x, 64);
-  if (live && inp == 0) {
-    const double avg = 0.25 * (p[0] + p[1] + p[2] + p[3]);
-    const double nan = __builtin_nan("");
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-      sm[(int64_t)(RYD_S_POP0 + x) * ldm + i] = p[x];
-      sm[(int64_t)(RYD_S_OV_RE0 + x) * ldm + i] = nan;
-      sm[(int64_t)(RYD_S_OV_IM0 + x) * ldm + i] = nan;
-    }
-    sm[(int64_t)RYD_S_AVG_POP * ldm + i] = avg;
-    sm[(int64_t)RYD_S_CTRL_PHASE * ldm + i] = nan;
-    sm[(int64_t)RYD_S_PENALTY * ldm + i] = nan;
-    sm[(int64_t)RYD_S_AVG_F * ldm + i] = avg;
-    sm[(int64_t)RYD_S_NMV_USEFUL * ldm + i] = 4.0 * nuse;
-    sm[(int64_t)RYD_S_NMV_EXEC * ldm + i] = 4.0 * nexec;
-    sm[(int64_t)RYD_S_TRACE11 * ldm + i] = tr11;
-    sm[(int64_t)RYD_S_NSQUARE * ldm + i] = 0.0;
-    status[i] = st_all;
-  }
+  lindblad_cheb_body<PROTO, SYM, Sector4>(prm, n, ldp, st, lds, sm, ldm, status, n_steps, shape);
 }
 
 // ---------------------------------------------------------------------------
@@ -2243,19 +2202,66 @@ __device__ __forceinline__ void apply_coh(const Gen& A0, const Gen& B0, const CG
   }
 }
 
-template <int PROTO, int KIND>
+// hilbert_space_dim = 3: per-atom q = 0 block {e00, e11, err, ex, ey}, q = -1 block
+// {|0><1|, |0><r|}, no extra parameter columns.
+struct Sector3 {
+  static constexpr int NB = 5;                 // q = 0 block of one atom
+  static constexpr int NS = NB * NB;           // the real (0,0) sector (state vector)
+  static constexpr int NROW = 2 * NB;          // complex coordinates of a row sector
+  struct Mj {};                                // the extra parameter columns: none
+  __device__ static __forceinline__ Mj load_mj(const double*, int64_t, int64_t) { return {}; }
+  __device__ static __forceinline__ bool mj_valid(const Mj&) { return true; }
+  __device__ static __forceinline__ bool mj_valid(bool ok, const Mj&) { return ok; }   // ok && mj_valid: gmj_valid
+  __device__ static __forceinline__ double rate_extra(const Mj&) { return 0.0; }   // their term of the rate sum
+  __host__ __device__ static constexpr bool population(int a) { return a < 3; }   // e00, e11, err
+
+  struct StateGen {
+    Gen A, B;
+  };
+  // SYM (identical atoms) is apply_L's to use: it reads A alone
+  template <bool SYM>
+  __device__ static __forceinline__ StateGen state_gen(const Seg& g, const PointP& q, const Mj&, double sc) {
+    return {make_gen(g, q.d1, q.gA, sc), make_gen(g, q.d1, q.gB, sc)};
+  }
+  template <bool SYM>
+  __device__ static __forceinline__ void state_apply(const StateGen& G, double vs, const double (&b)[NS],
+                                                     double (&o)[NS]) {
+    apply_L<SYM>(G.A, G.B, vs, b, o);
+  }
+
+  // sector KIND's generator blocks (KIND 0 reads A0 and Bm, KIND 1 B0 and Am, the quads Am and
+  // Bm; B's block conjugated for KIND 3, the (-1,+1) sector)
+  struct CohGen {
+    Gen A0, B0;
+    CGen Am, Bm;
+  };
+  template <int KIND>
+  __device__ static __forceinline__ CohGen coh_gen(const Seg& g, const PointP& q, const Mj&, double sc) {
+    return {make_gen(g, q.d1, q.gA, sc), make_gen(g, q.d1, q.gB, sc), make_cgen(g, q.d1, q.gA, sc, false),
+            make_cgen(g, q.d1, q.gB, sc, KIND == 3)};
+  }
+  template <int KIND>
+  __device__ static __forceinline__ void coh_apply(const CohGen& G, double vs, const double* b, double* o) {
+    apply_coh<KIND>(G.A0, G.B0, G.Am, G.Bm, vs, b, o);
+  }
+};
+
+// One lane per (point, input) of one sector, a Chebyshev series per segment.  The row sectors
+// (KIND 0 / 1) hold S::NROW complex coordinates, the quads 4.
+template <int PROTO, int KIND, typename S>
 __device__ __forceinline__ void coherence_sector(const double* __restrict__ prm, int64_t n, int64_t ldp,
                                                  double* __restrict__ out, int64_t ldo,
                                                  uint32_t* __restrict__ status, int n_steps, int shape,
                                                  int64_t blk) {
   constexpr int NIN = KIND < 2 ? 2 : 1;     // inputs of this sector per point
-  constexpr int NV = KIND < 2 ? 20 : 8;
+  constexpr int NV = KIND < 2 ? 2 * S::NROW : 8;
   const int64_t gid = blk * BLOCK + threadIdx.x;
   const bool live = gid < NIN * n;
   const int64_t i = live ? gid / NIN : (n - 1);
   const int sub = (int)(gid % NIN);
   const PointP q = load_point<PROTO>(prm, ldp, i);
-  const bool valid = point_valid<PROTO>(q, n_steps);
+  const typename S::Mj mj = S::load_mj(prm, ldp, i);
+  const bool valid = point_valid<PROTO>(q, n_steps) && S::mj_valid(mj);
   // start: KIND 0 C[sub][0] (|00><01|: e00 (x) |0><1| ; |10><11|: e11 (x) |0><1|),
   //        KIND 1 C[0][sub], KIND 2/3 C[0][0]
   const int e0 = KIND == 0 ? 4 * sub : (KIND == 1 ? 2 * sub : 0);
@@ -2265,26 +2271,23 @@ __device__ __forceinline__ void coherence_sector(const double* __restrict__ prm,
   double nuse = 0.0, nexec = 0.0;
   bool over_cap = false;
   const int nseg = n_segments<PROTO>(n_steps);
-  double rsum = 0.0;
+  double rsum = S::rate_extra(mj);
 #pragma unroll
   for (int c = 0; c < 4; ++c) rsum += fabs(q.gA[c]) + fabs(q.gB[c]);
+  // LP square's two segments of a quad sector (8 doubles) are unrolled -- said here because the
+  // compiler's own size estimate of that loop sits at its threshold; the other loops stay rolled
+  // (a count of 1 forbids unrolling them: what the compiler chose by itself for all of them,
+  // to be looked at again, with make kernel-diff, when the compiler changes)
+  constexpr int SEG_UNROLL = (KIND >= 2 && PROTO == RYD_PROTO_LP_SQUARE) ? 2 : 1;
+#pragma unroll SEG_UNROLL
   for (int s = 0; s < nseg; ++s) {
     const Seg g = segment<PROTO>(q, s, n_steps, shape);
-    double emin, emax;
-    h_bounds(g, q.V, q.d1, emin, emax);
-    const double omega = (emax - emin) + rsum;
-    const double x = omega * g.dt;
-    const bool capped = valid && !(x <= X_CAP);
-    const bool active = valid && !capped && x > X_SKIP;
-    over_cap = over_cap || capped;
-    const double sc = active ? 2.0 / omega : 0.0;
-    const Gen A0 = make_gen(g, q.d1, q.gA, sc);
-    const Gen B0 = make_gen(g, q.d1, q.gB, sc);
-    const CGen Am = make_cgen(g, q.d1, q.gA, sc, false);
-    const CGen Bm = make_cgen(g, q.d1, q.gB, sc, KIND == 3);
-    const double vs = sc * 0.5 * q.V;
-    cheb_segment<NV>(v, x, active,
-                     [&](const double (&b)[NV], double (&o)[NV]) { apply_coh<KIND>(A0, B0, Am, Bm, vs, b, o); },
+    const SegScale k = seg_scale(g, q.V, q.d1, rsum, valid);
+    over_cap = over_cap || k.capped;
+    const auto G = S::template coh_gen<KIND>(g, q, mj, k.sc);
+    const double vs = k.sc * 0.5 * q.V;
+    cheb_segment<NV>(v, k.x, k.active,
+                     [&](const double (&b)[NV], double (&o)[NV]) { S::template coh_apply<KIND>(G, vs, b, o); },
                      nuse, nexec);
   }
   uint32_t stat = valid ? 0u : RYD_STATUS_BAD_INPUT;
@@ -2314,17 +2317,25 @@ __device__ __forceinline__ void coherence_sector(const double* __restrict__ prm,
 // [b1, b2) sector 2, then sector 3 (block-uniform branch).  The sectors used to be four
 // back-to-back launches of 2n, 2n, n and n lanes -- each far below one wave per SIMD at
 // C2 sizes, so the device idled through four serial latency-bound tails; together they
-// fill the chip once (the two 20-double sectors, whose lanes run longest, first).
+// fill the chip once (the two row sectors, whose lanes run longest, first).
+template <int PROTO, typename S>
+__device__ __forceinline__ void coherence_cheb_body(const double* __restrict__ prm, int64_t n, int64_t ldp,
+                                                    double* __restrict__ out, int64_t ldo,
+                                                    uint32_t* __restrict__ status, int n_steps, int shape,
+                                                    int64_t b0, int64_t b1, int64_t b2) {
+  const int64_t b = blockIdx.x;
+  if (b < b0) coherence_sector<PROTO, 0, S>(prm, n, ldp, out, ldo, status, n_steps, shape, b);
+  else if (b < b1) coherence_sector<PROTO, 1, S>(prm, n, ldp, out, ldo, status, n_steps, shape, b - b0);
+  else if (b < b2) coherence_sector<PROTO, 2, S>(prm, n, ldp, out, ldo, status, n_steps, shape, b - b1);
+  else coherence_sector<PROTO, 3, S>(prm, n, ldp, out, ldo, status, n_steps, shape, b - b2);
+}
+
 template <int PROTO>
 __global__ __launch_bounds__(BLOCK) void coherence_cheb_kernel(const double* __restrict__ prm, int64_t n,
                                                                int64_t ldp, double* __restrict__ out, int64_t ldo,
                                                                uint32_t* __restrict__ status, int n_steps,
                                                                int shape, int64_t b0, int64_t b1, int64_t b2) {
-  const int64_t b = blockIdx.x;
-  if (b < b0) coherence_sector<PROTO, 0>(prm, n, ldp, out, ldo, status, n_steps, shape, b);
-  else if (b < b1) coherence_sector<PROTO, 1>(prm, n, ldp, out, ldo, status, n_steps, shape, b - b0);
-  else if (b < b2) coherence_sector<PROTO, 2>(prm, n, ldp, out, ldo, status, n_steps, shape, b - b1);
-  else coherence_sector<PROTO, 3>(prm, n, ldp, out, ldo, status, n_steps, shape, b - b2);
+  coherence_cheb_body<PROTO, Sector3>(prm, n, ldp, out, ldo, status, n_steps, shape, b0, b1, b2);
 }
 
 #include "ryd_coh_prop.inc"

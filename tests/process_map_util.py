@@ -1,5 +1,7 @@
 """Shared helpers for the process-map tests: oracle PointSpec from packed params and
 the GPU output rows an exact map corresponds to (so host code is testable on CPU)."""
+import os
+
 import numpy as np
 
 from noisyquantumsimulator_amd import _native as N
@@ -57,3 +59,24 @@ def unitary_map(U):
             X[a, b] = 1
             S[:, 4 * a + b] = (U @ X @ U.conj().T).reshape(-1)
     return S
+
+
+class coh_path:
+    """RYD_COH_PROP for the block: None = the default (propagator) path, "0" = the per-lane
+    Chebyshev kernel.  Restored on exit."""
+
+    def __init__(self, value):
+        self.value = value
+
+    def __enter__(self):
+        self.old = os.environ.pop("RYD_COH_PROP", None)
+        if self.value is not None:
+            os.environ["RYD_COH_PROP"] = self.value
+
+    def __exit__(self, *exc):
+        os.environ.pop("RYD_COH_PROP", None)
+        if self.old is not None:
+            os.environ["RYD_COH_PROP"] = self.old
+
+
+PATHS = (None, "0")

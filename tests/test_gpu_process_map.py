@@ -1,14 +1,21 @@
 """Process maps on the GPU (ryd_run_coherences + the diagonal sector) against the
 oracle's full-Liouvillian definition.  Tolerance 1e-10 on every
-map element, as the state parity tests."""
+map element, as the state parity tests.  The oracle comparisons run on both coherence
+paths: coherence_prop_kernel (the default) and coherence_cheb_kernel (RYD_COH_PROP=0)."""
+import warnings
+
 import numpy as np
 import pytest
 
+import oracle_evaluator as OE
 from noisyquantumsimulator_amd import _native as N
+from noisyquantumsimulator_amd import configurations as CF
 from noisyquantumsimulator_amd import engine as E
 from noisyquantumsimulator_amd import noise_models as NM
+from noisyquantumsimulator_amd import physics as PH
 from oracle import lindblad_oracle as O
-from process_map_util import spec_from_params
+from process_map4_util import lp_shaped_segments, process_map_dim
+from process_map_util import PATHS, coh_path, spec_from_params
 from test_gpu_parity import _random_points
 
 pytestmark = pytest.mark.gpu
@@ -21,16 +28,26 @@ def eng():
     return E.Engine()
 
 
+def _both_paths_match_oracle(eng, p, protocol, n_steps, what):
+    """Every point's map against the oracle's (computed once) on both coherence paths."""
+    n = p.shape[1]
+    ref = [O.process_map(spec_from_params(p, i, protocol, n_steps=n_steps or 300)) for i in range(n)]
+    for path in PATHS:
+        with coh_path(path):
+            pm = NM.gate_process_maps(p, protocol, n_steps=n_steps, engine=eng, with_kraus=True)
+        assert np.all(pm.status == 0)
+        for i in range(n):
+            print(f"{protocol} {what} RYD_COH_PROP={path} point {i}: max|dS| = {np.abs(pm.S[i] - ref[i]).max():.3e}")
+        for i in range(n):
+            np.testing.assert_allclose(pm.S[i], ref[i], atol=TOL, rtol=0, err_msg=f"{protocol}/{path}/{i}")
+        assert np.all(pm.kraus_rank > 1)                  # noisy: not a unitary channel
+
+
 @pytest.mark.parametrize("protocol,n_steps", [("lp_square", None), ("smooth_jp", 30), ("bangbang", None)])
 def test_process_map_matches_oracle(eng, protocol, n_steps):
     rng = np.random.default_rng(99)
     p = _random_points(rng, 5, protocol)                 # asymmetric atoms, random rates
-    pm = NM.gate_process_maps(p, protocol, n_steps=n_steps, engine=eng, with_kraus=True)
-    assert np.all(pm.status == 0)
-    for i in range(5):
-        ref = O.process_map(spec_from_params(p, i, protocol, n_steps=n_steps or 300))
-        np.testing.assert_allclose(pm.S[i], ref, atol=TOL, rtol=0)
-    assert np.all(pm.kraus_rank > 1)                      # noisy: not a unitary channel
+    _both_paths_match_oracle(eng, p, protocol, n_steps, "unequal atoms")
 
 
 @pytest.mark.parametrize("protocol,n_steps", [("lp_square", None), ("smooth_jp", 30), ("bangbang", None)])
@@ -42,13 +59,32 @@ def test_process_map_identical_atoms_matches_oracle(eng, protocol, n_steps):
     for k in ("G1", "G0", "GPHI", "GSC"):
         p[N.P[k + "_B"]] = p[N.P[k + "_A"]]
     assert E.symmetric_atoms(p)
-    pm = NM.gate_process_maps(p, protocol, n_steps=n_steps, engine=eng, with_kraus=True)
+    _both_paths_match_oracle(eng, p, protocol, n_steps, "identical atoms")
+
+
+def test_shaped_lp_process_map_matches_oracle(eng):
+    """A cosine envelope: a new amplitude every segment, so coherence_cheb_kernel whatever
+    RYD_COH_PROP says.  3 derived points (temperatures and laser power spread as in the dim-4
+    twin of this test), 2 x 11 segments."""
+    n = 3
+    exc = CF.TwoPhotonExcitationConfig(
+        laser_1=CF.LaserParameters(power=50e-6, waist=50e-6, polarization="pi", polarization_purity=0.95),
+        laser_2=CF.LaserParameters(power=0.3, waist=50e-6, polarization="sigma+", polarization_purity=0.95))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        b = PH.derive_batch(CF.LPSimulationInputs(excitation=exc, pulse_shape="cosine"), n, hilbert_space_dim=3,
+                            species="Rb87", n_rydberg=70, tweezer_power=0.020, tweezer_waist=0.8e-6,
+                            spacing_factor=2.8, B_field=1e-4, NA=0.5, temperature=np.linspace(1e-6, 3e-5, n),
+                            overrides=dict(laser_2_power=np.geomspace(0.03, 3.0, n)))
+    assert E.protocol_key(b) == "lp_shaped"
+    pm = NM.gate_process_maps(E.pack_params(b), "lp_shaped", n_steps=12, shape="cosine", engine=eng)
     assert np.all(pm.status == 0)
-    for i in range(5):
-        ref = O.process_map(spec_from_params(p, i, protocol, n_steps=n_steps or 300))
-        print(f"{protocol} identical atoms, point {i}: max|dS| = {np.abs(pm.S[i] - ref).max():.3e}")
+    for i in range(n):
+        spec = OE.point_spec(b, i)
+        assert spec.protocol == "lp_shaped" and spec.pulse_shape == "cosine" and spec.dim == 3
+        ref = process_map_dim(spec, lp_shaped_segments(spec, 12))
+        print(f"shaped point {i}: max|dS| = {np.abs(pm.S[i] - ref).max():.3e}")
         np.testing.assert_allclose(pm.S[i], ref, atol=TOL, rtol=0)
-    assert np.all(pm.kraus_rank > 1)
 
 
 def test_noise_free_map_is_the_ket_unitary(eng):

@@ -4,7 +4,6 @@ Liouvillian.  Tolerance 1e-10 on every map element, 1e-9 on fidelities.  Shapes 
 and chosen for the kernel's layout: 4 points per wave, per-row squaring depths, a ragged
 last wave, the bank-masked quads, the identical-atom mirror."""
 import json
-import os
 import warnings
 
 import numpy as np
@@ -19,6 +18,7 @@ from noisyquantumsimulator_amd import noise_models as NM
 from noisyquantumsimulator_amd import physics as PH
 from noisyquantumsimulator_amd import simulation as SIM
 from process_map4_util import lp_shaped_segments, process_map_dim, spec4_from_params
+from process_map_util import PATHS, coh_path as _coh_path
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
@@ -43,27 +43,6 @@ def _batch(si, n, **kw):
         return PH.derive_batch(si, n, hilbert_space_dim=4,
                                **dict(KW, temperature=np.linspace(1e-6, 3e-5, n)),
                                overrides=dict(laser_2_power=np.geomspace(0.03, 3.0, n)), **kw)
-
-
-class _coh_path:
-    """RYD_COH_PROP for the block: None = the default (propagator) path, "0" = the per-lane
-    Chebyshev kernel.  Restored on exit."""
-
-    def __init__(self, value):
-        self.value = value
-
-    def __enter__(self):
-        self.old = os.environ.pop("RYD_COH_PROP", None)
-        if self.value is not None:
-            os.environ["RYD_COH_PROP"] = self.value
-
-    def __exit__(self, *exc):
-        os.environ.pop("RYD_COH_PROP", None)
-        if self.old is not None:
-            os.environ["RYD_COH_PROP"] = self.old
-
-
-PATHS = (None, "0")
 
 
 @pytest.fixture(scope="module")
