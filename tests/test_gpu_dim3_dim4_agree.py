@@ -6,6 +6,8 @@ maps on these parameter columns agree to 1e-13.)"""
 import numpy as np
 import pytest
 
+import coh_points as CP
+import dim4_points as D4
 from noisyquantumsimulator_amd import _native as N
 from noisyquantumsimulator_amd import engine as E
 from process_map_util import PATHS, coh_path
@@ -44,6 +46,46 @@ def test_coherence_rows_agree_across_dimensions(eng, protocol, n_steps, identica
         print(f"{protocol} RYD_COH_PROP={path}: max|coh4 - coh3| per point = "
               f"{np.abs(c4 - c3).max(axis=0)}")
         np.testing.assert_allclose(c4, c3, atol=TOL, rtol=0, err_msg=f"{protocol}/{path}")
+
+
+def _strong_points(protocol, identical):
+    """Five "strong" points (V / Omega 0.3 ... 30, rates that are percents of Omega: every
+    sector coordinate is large against TOL) with the GMJ columns zeroed."""
+    seed = 20261110 + [c[0] for c in CASES].index(protocol)
+    p = CP.twin3(D4.random_points4(np.random.default_rng(seed), 5, protocol, "strong"))
+    if identical:
+        p = D4.sym(p)
+    assert E.symmetric_atoms(p) == identical
+    return p
+
+
+@pytest.mark.parametrize("identical", [False, True], ids=["unequal", "identical"])
+@pytest.mark.parametrize("protocol,n_steps", CASES)
+def test_strong_coherence_rows_agree_across_dimensions(eng, protocol, n_steps, identical):
+    p = _strong_points(protocol, identical)
+    for path in PATHS:
+        with coh_path(path):
+            c3, s3 = eng.run_coherences(p, protocol, n_steps=n_steps, dim=3)
+            c4, s4 = eng.run_coherences(p, protocol, n_steps=n_steps, dim=4)
+        assert np.all(s3 == 0) and np.all(s4 == 0)
+        print(f"strong {protocol} RYD_COH_PROP={path}: max|coh4 - coh3| per point = "
+              f"{np.abs(c4 - c3).max(axis=0)}")
+        np.testing.assert_allclose(c4, c3, atol=TOL, rtol=0, err_msg=f"{protocol}/{path}")
+
+
+def test_x_ladder_twin_agrees_across_dimensions(eng):
+    """The x ladder's dim-3 twin: every series degree without squarings and the identity build,
+    through both dimensions' kernels on the same columns."""
+    p = CP.twin3(D4.x_ladder4())
+    for path in PATHS:
+        with coh_path(path):
+            c3, s3 = eng.run_coherences(p, "lp_square", dim=3)
+            c4, s4 = eng.run_coherences(p, "lp_square", dim=4)
+        assert np.all(s3 == 0) and np.all(s4 == 0)
+        print(f"x ladder twin RYD_COH_PROP={path}: max|coh4 - coh3| = {np.abs(c4 - c3).max():.3e}")
+        np.testing.assert_allclose(c4, c3, atol=TOL, rtol=0, err_msg=f"x ladder twin/{path}")
+        np.testing.assert_array_equal(c3[:, -1], CP.identity_rows())
+        np.testing.assert_array_equal(c4[:, -1], CP.identity_rows())
 
 
 @pytest.mark.parametrize("identical", [False, True], ids=["unequal", "identical"])
