@@ -283,6 +283,19 @@ int         ryd_summary_width(void);
 int         ryd_state_width(int evolution, int dim);
 /* squaring levels the identical-atom LP-square kernel leaves unsquared (see RYD_S_NSQUARE) */
 int         ryd_lp_unsquared(void);
+/* The static plan of the identical-atom LP-square kernel's CU-balanced launch form for n
+ * points on `cus` compute units (pure host code, no device needed): workgroups of
+ * gpc = ceil(groups / cus) four-point groups (gpc_override 1..16 replaces it, 0 = none),
+ * each wave of a workgroup a whole job (role 0), or the producer (1) or consumer (2) half of
+ * a split job.  head[5] = groups, workgroups, waves per workgroup, gpc, 1 if the automatic
+ * rule picks the form for this n.  role/job/present[workgroup * waves + wave] (capacity
+ * `cap` entries; may be NULL): the wave's role, its group index, and 0 where that index
+ * lies past the batch (the wave returns at once).  Returns the entry count, -1 on bad
+ * arguments.  RYD_S16_BALANCE=0 disables the form, =2 forces it for every LP-square launch
+ * of that kernel, RYD_S16_BALANCE_GPC overrides gpc, RYD_S16_BALANCE_NOHANDOFF=1 makes
+ * every consumer compute the producer's part itself (read per launch). */
+int64_t     ryd_sym16_balance_plan(int64_t n, int cus, int gpc_override, int64_t* head, int32_t* role,
+                                   int64_t* job, uint8_t* present, int64_t cap);
 int         ryd_device_count(int* count);
 
 int ryd_create(const int* device_ids, int n_devices, ryd_handle** out);

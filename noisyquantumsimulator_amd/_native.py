@@ -59,6 +59,7 @@ T_FLAG = {"auto": 0, "rows": 1, "lanes": 2}
 TL_HEAD, TL_SLOT = 4, 8
 
 EXPORTED = ("ryd_abi_version", "ryd_last_error", "ryd_param_count", "ryd_summary_width", "ryd_lp_unsquared",
+            "ryd_sym16_balance_plan",
             "ryd_state_width", "ryd_device_count", "ryd_create", "ryd_destroy", "ryd_run_batch",
             "ryd_run_batch_device", "ryd_run_coherences", "ryd_run_coherences_device",
             "ryd_run_trajectories", "ryd_run_trajectories_device",
@@ -148,6 +149,10 @@ def load() -> ctypes.CDLL:
         lib.ryd_param_count.restype = ctypes.c_int
         lib.ryd_summary_width.restype = ctypes.c_int
         lib.ryd_lp_unsquared.restype = ctypes.c_int
+        lib.ryd_sym16_balance_plan.restype = ctypes.c_int64
+        lib.ryd_sym16_balance_plan.argtypes = [i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(i64),
+                                               ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(i64),
+                                               ctypes.POINTER(ctypes.c_uint8), i64]
         lib.ryd_state_width.argtypes = [ctypes.c_int, ctypes.c_int]
         lib.ryd_device_count.argtypes = [ctypes.POINTER(ctypes.c_int)]
         lib.ryd_create.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(vp)]

@@ -2396,6 +2396,48 @@ bool sym16_store32_enabled() {
   return !(e && e[0] == '1');
 }
 
+// The balanced launch form of the sym16 LP-square kernel (ryd_sym16.inc): the static plan
+// for n points on `cus` compute units.  gpc_override > 0 sets the groups per workgroup.
+// auto_on: the launches the form is measured to win -- every wave resident at once, more
+// than one job per SIMD, and 1 or 2 jobs per CU left over beyond a multiple of 4 (C2's
+// 10,000 points: 10 groups per CU; profiles/sym16_balance/ab_sizes.txt).
+struct S16Plan {
+  int64_t groups, workgroups;
+  int gpc, waves;
+  bool auto_on;
+};
+bool sym16_plan(int64_t n, int cus, int gpc_override, S16Plan* pl) {
+  if (n <= 0 || cus <= 0 || gpc_override < 0 || gpc_override > S16_BAL_MAXW) return false;
+  const int64_t G = (n + S16_PPW - 1) / S16_PPW;
+  const int64_t natural = (G + cus - 1) / cus;
+  const int gnat = (int)(natural < S16_BAL_MAXW ? natural : S16_BAL_MAXW);
+  pl->groups = G;
+  pl->gpc = gpc_override > 0 ? gpc_override : gnat;
+  pl->workgroups = (G + pl->gpc - 1) / pl->gpc;
+  pl->waves = s16_bal_waves(pl->gpc);
+  pl->auto_on = natural <= S16_BAL_MAXW && gnat > 4 && s16_bal_split(gnat);
+  return true;
+}
+
+// RYD_S16_BALANCE: 0 never, 2 always (LP square on the sym16 path, any n), otherwise auto;
+// RYD_S16_BALANCE_GPC=<k> overrides the groups per workgroup; RYD_S16_BALANCE_NOHANDOFF=1
+// makes every consumer run the producer's part itself (tests).  Read per launch.
+int sym16_balance_mode() {
+  const char* e = getenv("RYD_S16_BALANCE");
+  return e && e[0] == '0' ? 0 : e && e[0] == '2' ? 2 : 1;
+}
+int sym16_device_cus() {
+  static std::atomic<int> cached[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  int c = cached[dev].load(std::memory_order_relaxed);
+  if (c == 0) {
+    if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    cached[dev].store(c, std::memory_order_relaxed);
+  }
+  return c;
+}
+
 // LP shaped, identical atoms, the auto method: the 16-lane DPP-row state-vector kernel
 // (ryd_shaped16.inc); RYD_SHAPED16=0 keeps lindblad_cheb_kernel (the cross-check)
 bool use_shaped16(const ryd_batch_desc* d) {
@@ -2642,6 +2684,36 @@ int launch(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, do
     // largest one fits: 8 (15 + 3 lds) on the state rows, 8 (15 ldm + 3) on the summary
     int st32 = sym16_store32_enabled() && lds >= 0 && ldm >= 0 && lds <= (0x1fffffffLL - 15) / 3 &&
                ldm <= (0x1fffffffLL - 3) / 15;
+    const int bal = d->protocol == RYD_PROTO_LP_SQUARE ? sym16_balance_mode() : 0;
+    if (bal != 0) {
+      // the form is chosen first (forced, or the automatic rule on this device's CU count);
+      // the other switches are read, and checked, only by a launch that takes it
+      const int cus = sym16_device_cus();
+      S16Plan pl;
+      const bool planned = sym16_plan(n, cus, 0, &pl);
+      if (bal == 2 && !planned)
+        return fail(RYD_ERR_HIP, "RYD_S16_BALANCE=2: the device's compute-unit count is not available");
+      if (planned && (bal == 2 || pl.auto_on)) {
+        if (const char* eg = getenv("RYD_S16_BALANCE_GPC")) {
+          char* end = nullptr;
+          const long over = strtol(eg, &end, 10);
+          if (end == eg || *end != '\0' || over < 1 || over > S16_BAL_MAXW)
+            return fail(RYD_ERR_INVALID, "RYD_S16_BALANCE_GPC must be an integer from 1 to 16");
+          sym16_plan(n, cus, (int)over, &pl);
+        }
+        const char* eh = getenv("RYD_S16_BALANCE_NOHANDOFF");
+        if (pl.workgroups > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
+        using BFn = void (*)(const double*, int64_t, int64_t, double*, int64_t, double*, int64_t, uint32_t*,
+                             int, int, int, int);
+        BFn fb = lindblad_sym16_kernel<RYD_PROTO_LP_SQUARE, 1>;
+        int gpc = pl.gpc, noh = eh && eh[0] == '1';
+        void* bargs[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&ds, (void*)&lds, (void*)&dm,
+                         (void*)&ldm, (void*)&dstat, (void*)&ns, (void*)&gpc, (void*)&st32, (void*)&noh};
+        HIPCHK(hipLaunchKernel((const void*)fb, dim3((unsigned)pl.workgroups), dim3(S16_BLOCK * pl.waves), bargs,
+                               0, stream));
+        return RYD_OK;
+      }
+    }
     void* args[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&ds, (void*)&lds, (void*)&dm,
                     (void*)&ldm, (void*)&dstat, (void*)&ns, (void*)&sh, (void*)&st32};
     HIPCHK(hipLaunchKernel((const void*)f, dim3((unsigned)blocks), dim3(S16_BLOCK), args, 0, stream));
@@ -3100,6 +3172,28 @@ const char* ryd_last_error(void) { return g_err.c_str(); }
 int ryd_param_count(void) { return RYD_NPARAM; }
 int ryd_summary_width(void) { return RYD_NSUMMARY; }
 int ryd_lp_unsquared(void) { return RYD_LP_UNSQUARED; }
+
+int64_t ryd_sym16_balance_plan(int64_t n, int cus, int gpc_override, int64_t* head, int32_t* role, int64_t* job,
+                               uint8_t* present, int64_t cap) {
+  S16Plan pl;
+  if (!head || !sym16_plan(n, cus, gpc_override, &pl)) return -1;
+  head[0] = pl.groups;
+  head[1] = pl.workgroups;
+  head[2] = pl.waves;
+  head[3] = pl.gpc;
+  head[4] = pl.auto_on ? 1 : 0;
+  const int64_t need = pl.workgroups * pl.waves;
+  if (!role || !job || !present || cap < need) return need;
+  for (int64_t b = 0; b < pl.workgroups; ++b)
+    for (int w = 0; w < pl.waves; ++w) {
+      const S16Role r = s16_bal_role(pl.gpc, w);
+      const int64_t j = s16_bal_job(b, pl.workgroups, r.off);   // the kernel's own expressions
+      role[b * pl.waves + w] = r.role;
+      job[b * pl.waves + w] = j;
+      present[b * pl.waves + w] = j < pl.groups ? 1 : 0;
+    }
+  return need;
+}
 int ryd_state_width(int evolution, int dim) {
   if (dim != 3 && dim != 4) return -1;
   if (evolution == RYD_EVOL_LINDBLAD) return dim == 3 ? 25 : 36;

@@ -80,7 +80,7 @@ __device__ __forceinline__ bool s16_one_round() {
 #ifndef RYD_XCD_MAP
 #define RYD_XCD_MAP 2
 #endif
-__device__ __forceinline__ int64_t xcd_block(int64_t b, int64_t nb) {
+__host__ __device__ __forceinline__ int64_t xcd_block(int64_t b, int64_t nb) {
   if (RYD_XCD_MAP == 0) return b;
   if (RYD_XCD_MAP == 1) {                    // one contiguous range per XCD
     const int64_t q = nb / 8, rem = nb % 8, x = b % 8, k = b / 8;
@@ -590,6 +590,98 @@ __host__ __device__ constexpr int seg_old(int n) {      // plain segment coordin
        : n == 7 ? 8 : n == 8 ? 10 : n == 9 ? 11 : n == 12 ? 6 : n == 13 ? 9 : 0;
 }
 
+// ---- the CU-balanced launch form (LP square, small launches) -------------------------
+// One workgroup per CU runs `gpc` four-point groups, strided over the batch: workgroup b of W
+// takes the groups k W + xcd_block(b, W), k < gpc (s16_bal_job).  Consecutive groups cost
+// alike (C2: a row of the grid shares its Rabi frequency, hence its squaring depth), so gpc
+// consecutive ones would load whole CUs heavy or light; the stride gives every CU a sample of
+// the sweep, and xcd_block keeps the four groups of a 128-byte parameter line on one XCD as
+// in the one-wave kernel.  Wave w of a workgroup
+// takes its role from its index alone: the first waves run one whole job each (the
+// one-wave kernel's body); when 1 or 2 jobs are left over beyond a multiple of 4, each of
+// them is split in time between a PRODUCER wave (parameter load to S16_BAL_HSQ squarings
+// into build16, the 15 column registers per lane parked in LDS) and a CONSUMER wave (the
+// rest of the job), so that with round-robin wave placement the four SIMDs of a CU carry
+// gpc / 4 jobs each (C2: 10 groups per CU -> 8 whole waves, 2 producers, 2 consumers, 2.5
+// jobs per SIMD instead of 3, 3, 2, 2).  The schedule is static -- no queue, no counter --
+// and correctness does not depend on where the waves land.  s16_bal_role is the one role
+// table: the kernel and the host plan (ryd_sym16_balance_plan) both evaluate it.
+constexpr int S16_BAL_MAXW = 16;             // waves per workgroup at most (gpc <= 16)
+constexpr int S16_BAL_WHOLE = 0, S16_BAL_PRODUCER = 1, S16_BAL_CONSUMER = 2;
+#ifndef RYD_S16_BAL_HSQ
+#define RYD_S16_BAL_HSQ 2                    // squarings before the handoff (even: the ping-pong pairs stay
+                                             // whole); 0, 2, 4 measured: profiles/sym16_balance/tuning.txt
+#endif
+static_assert(RYD_S16_BAL_HSQ >= 0 && RYD_S16_BAL_HSQ % 2 == 0, "handoff after whole squaring pairs");
+#ifndef RYD_S16_BAL_POLLS
+#define RYD_S16_BAL_POLLS 4096               // a consumer's polls before it runs the producer's part itself
+#endif
+#ifdef RYD_S16_PROF
+constexpr int S16_BAL_NCNT = 4;
+#else
+constexpr int S16_BAL_NCNT = 2;
+#endif
+struct S16Role {
+  int role, off;                             // the workgroup's off-th job; a split job's slot = off - (gpc & ~3)
+};
+__host__ __device__ __forceinline__ int64_t s16_bal_job(int64_t wg, int64_t nwg, int off) {
+  return (int64_t)off * nwg + xcd_block(wg, nwg);
+}
+__host__ __device__ constexpr bool s16_bal_split(int gpc) { return (gpc & 3) == 1 || (gpc & 3) == 2; }
+__host__ __device__ constexpr int s16_bal_waves(int gpc) { return gpc + (s16_bal_split(gpc) ? (gpc & 3) : 0); }
+__host__ __device__ constexpr S16Role s16_bal_role(int gpc, int w) {
+  const int rem = gpc & 3, nwhole = s16_bal_split(gpc) ? gpc - rem : gpc;
+  if (w < nwhole) return {S16_BAL_WHOLE, w};
+  if (w < nwhole + rem) return {S16_BAL_PRODUCER, w};
+  return {S16_BAL_CONSUMER, w - rem};
+}
+
+// build16's view of a split job (S16NoHandoff: the whole build, today's code)
+struct S16NoHandoff {};
+struct S16Handoff {
+  int role, slot;
+  bool poll;                                 // false: the consumer takes the fallback at once
+  double (&cols)[2][NS][64];                 // [slot][column entry][lane]
+  int (&cnt)[2][S16_BAL_NCNT][64];           // nuse, nexec (PROF build: and the producer's stamps)
+  int (&flag)[2];
+  int* polls;                                // PROF build: polls made, fallback taken
+};
+
+// The consumer's wait: the producer's flag (LDS, workgroup scope) polled a bounded number
+// of times with the wave asleep in between.  false = still clear: the caller runs the
+// producer's part itself and never reads the slot, so no wait outlasts the bound and the
+// result does not depend on the outcome.
+__device__ __forceinline__ bool s16_wait_flag(int* f, int* polls) {
+  for (int i = 0; i < RYD_S16_BAL_POLLS; ++i) {
+    const int v = __hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (__builtin_amdgcn_readfirstlane(v) != 0) {
+      if (polls) *polls = i + 1;
+      return true;
+    }
+    __builtin_amdgcn_s_sleep(4);
+  }
+  if (polls) *polls = -RYD_S16_BAL_POLLS;
+  return false;
+}
+
+// Issue priorities of the balanced form.  A split job is the launch's longest dependency
+// chain (two waves run it one after the other, the second starts late), so its producer and
+// its consumer keep the highest priority from start to end, and the whole-job waves run the
+// one-round schedule's phase-stepped levels lowered by RYD_S16_BAL_PRIO_DROP: they fill the
+// issue slots the split job leaves.
+#ifndef RYD_S16_BAL_PRIO_DROP
+#define RYD_S16_BAL_PRIO_DROP 0
+#endif
+template <int LEVEL, typename HO>
+__device__ __forceinline__ void s16_phase_prio(const HO& ho) {
+  if constexpr (std::is_same<HO, S16NoHandoff>::value) {
+    S16_PRIO(LEVEL);
+  } else {
+    if (ho.role == S16_BAL_WHOLE)
+      __builtin_amdgcn_s_setprio(LEVEL > RYD_S16_BAL_PRIO_DROP ? LEVEL - RYD_S16_BAL_PRIO_DROP : 0);
+  }
+}
+
 // Build this point's phase-0 propagator for (amplitude a, detuning dl, duration dt)
 // and leave row r of it in u (identity when the point is invalid or the segment is
 // empty).  Called by the whole wave in uniform control flow; `count` = this point
@@ -598,10 +690,17 @@ __host__ __device__ constexpr int seg_old(int n) {      // plain segment coordin
 // rep = min(s, keep), and the caller applies it 2^rep times per segment (for the few
 // states of LP square, 2^rep - 1 extra row updates cost less than `keep` squarings).
 // nsq counts the full depth s (RYD_S_NSQUARE).  nrep = the wave's largest rep.
-__device__ __forceinline__ void build16(double (&u)[NS], double (&Ut)[S16_PPW][NS][16], const PointP& q,
+// HO = S16Handoff (the balanced form's first build): a producer wave leaves after the series
+// and min(RYD_S16_BAL_HSQ, the wave's squaring count) squarings, its columns and series
+// counters parked in the job's LDS slot, and returns true (the wave is done); a consumer
+// repeats the set-up arithmetic (the same instructions, the same bits), takes the columns
+// from the slot and goes on from there -- or, its wait exhausted, runs everything itself.
+template <typename HO = S16NoHandoff>
+__device__ __forceinline__ bool build16(double (&u)[NS], double (&Ut)[S16_PPW][NS][16], const PointP& q,
                                         bool valid, bool count, double a, double dl, double dt, int p, int r,
                                         int keep, int& rep, int& nrep, int& nuse, int& nexec, int& nsq,
-                                        bool& over_cap, lds_zero_t* zl S16_PROF_ARG) {
+                                        bool& over_cap, lds_zero_t* zl S16_PROF_ARG, const HO& ho = HO{}) {
+  constexpr bool SPLIT = !std::is_same<HO, S16NoHandoff>::value;
   const bool lane_ok = r < NS;
   Seg g;
   g.om_re = a;
@@ -659,11 +758,19 @@ __device__ __forceinline__ void build16(double (&u)[NS], double (&Ut)[S16_PPW][N
   // ---- (1) Chebyshev column r of exp(y L) on the triangle
   double v[NS];
   const int nuse0 = nuse;
-  cheb_unit16(v, r, y, act && lane_ok,
-              [&](const double (&b)[NS], double (&o)[NS]) { apply_Lsym_re(A, vs, b, o); }, nuse, nexec, zl);
-  if (!count) nuse = nuse0;                  // each distinct propagator counted once
+  bool have = false;                         // the columns come from the producer's slot
+  bool producer = false;
+  if constexpr (SPLIT) {
+    producer = ho.role == S16_BAL_PRODUCER;
+    if (ho.role == S16_BAL_CONSUMER && ho.poll) have = s16_wait_flag(&ho.flag[ho.slot], ho.polls);
+  }
+  if (!SPLIT || !have) {
+    cheb_unit16(v, r, y, act && lane_ok,
+                [&](const double (&b)[NS], double (&o)[NS]) { apply_Lsym_re(A, vs, b, o); }, nuse, nexec, zl);
+    if (!count) nuse = nuse0;                // each distinct propagator counted once
+  }
   S16_MARK(2);
-  S16_PRIO(2);
+  s16_phase_prio<2>(ho);
   // ---- (2) squarings, column-held, DPP broadcasts within the row
   // one reduction of the full depth serves both loops: sq and rep are monotone in sqf, so
   // their maxima over the wave are the same functions of the largest depth
@@ -674,10 +781,23 @@ __device__ __forceinline__ void build16(double (&u)[NS], double (&Ut)[S16_PPW][N
 #else
   const int smx = min(sfm > keep ? sfm - keep : 0, RYD_S16_SQ_CAP);
 #endif
+  int it0 = 0, it1 = smx;                    // the squarings this wave runs
+  if constexpr (SPLIT) {
+    const int hs = min((int)RYD_S16_BAL_HSQ, smx);     // a shallower wave hands over where it ends
+    const int l = 16 * p + r;
+    if (producer) it1 = hs;
+    if (have) {
+      it0 = hs;
+#pragma unroll
+      for (int k = 0; k < NS; ++k) v[k] = ho.cols[ho.slot][k][l];
+      nuse = ho.cnt[ho.slot][0][l];          // what cheb_unit16 left in the producer (count = valid there too)
+      nexec = ho.cnt[ho.slot][1][l];
+    }
+  }
   {
-    for (int it = 0; it < smx; it += 2) {
+    for (int it = it0; it < it1; it += 2) {
       double w[NS];                          // ping-pong: v -> w -> v (nothing carried in w)
-      if (RYD_S16_PRIO_SPLIT && it == ((smx >> 1) & ~1)) S16_PRIO(1);   // second half of the squarings
+      if (RYD_S16_PRIO_SPLIT && it == ((smx >> 1) & ~1)) s16_phase_prio<1>(ho);   // second half of the squarings
       if (it < sq) square_cols16(v, w, zl);
       if (it + 1 < sq) {
         square_cols16(w, v, zl);
@@ -687,9 +807,27 @@ __device__ __forceinline__ void build16(double (&u)[NS], double (&Ut)[S16_PPW][N
       }
     }
   }
+  if constexpr (SPLIT) {
+    if (producer) {
+      // park the columns and the series counters, then publish: the release orders the
+      // slot's LDS writes before the flag for the consumer's acquire.  Nothing is awaited.
+      const int l = 16 * p + r;
+#pragma unroll
+      for (int k = 0; k < NS; ++k) ho.cols[ho.slot][k][l] = v[k];
+      ho.cnt[ho.slot][0][l] = nuse;
+      ho.cnt[ho.slot][1][l] = nexec;
+#ifdef RYD_S16_PROF
+      S16_MARK(3);
+      ho.cnt[ho.slot][2][l] = (int)(s16_ts[3] - s16_ts[0]);
+      ho.cnt[ho.slot][3][l] = (int)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));
+#endif
+      __hip_atomic_store(&ho.flag[ho.slot], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      return true;
+    }
+  }
   if (count) nsq += sqf;
   S16_MARK(3);
-  S16_PRIO(1);
+  s16_phase_prio<1>(ho);
   // ---- (3) transpose through LDS: lane r takes row r of U' = S U S^-1 (segment order)
   wave_sync();
   if (lane_ok) {
@@ -722,7 +860,8 @@ __device__ __forceinline__ void build16(double (&u)[NS], double (&Ut)[S16_PPW][N
     else u[nn] = R[seg_old(nn)];
   });
   S16_MARK(4);
-  S16_PRIO(0);
+  s16_phase_prio<0>(ho);
+  return false;
 }
 
 // Lane weights of the state rotation T(c, s) in segment order: t' = al t + be t[lane ^ 1]
@@ -861,286 +1000,22 @@ __global__ __launch_bounds__(S16_BLOCK) __attribute__((amdgpu_waves_per_eu(PROTO
 lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st,
                       int64_t lds, double* __restrict__ sm, int64_t ldm, uint32_t* __restrict__ status,
                       int n_steps, int shape, int st32) {
-  __shared__ __attribute__((aligned(16))) double Ut[S16_PPW][NS][16];     // transpose, then output staging
-  static_assert(sizeof(Ut) >= sizeof(double) * S16_PPW * 4 * NC, "output staging must fit in Ut");
   (void)shape;
-#ifdef RYD_S16_PROF
-  double s16_ts[10];
-  s16_ts[8] = (double)__builtin_amdgcn_s_memrealtime();
-  S16_MARK(0);
-#endif
-  __shared__ double Zl[16];                  // zero words: squaring accumulator clears, lane 15's row
-  const int l = threadIdx.x;
-  const int p = l >> 4, r = l & 15;
-  if (l < 16) Zl[l] = 0.0;                   // same wave: ordered before the first squaring
-  // the wave's first point (uniform, 64-bit) and this lane's byte offset from it, clamped
-  // to the batch: every parameter address is an SGPR base plus this 32-bit offset
-  const int64_t b0 = xcd_block(blockIdx.x, gridDim.x) * S16_PPW;
-  const int64_t i0 = b0 < n ? b0 : n - 1;    // a wave past the batch (padded grid) reads point n-1
-  const int64_t last = n - 1 - i0;           // >= 0
-  const unsigned po8 = 8u * (unsigned)min(p, last < S16_PPW - 1 ? (int)last : S16_PPW - 1);
-  // loaded and validated once; the segment-0 build takes its inputs from here
-  const PointP q0 = load_point16<PROTO>(prm, ldp, i0, po8);
-  const bool valid = point_valid<PROTO>(q0, n_steps);
-  const bool frame_ok =
-      !(PROTO == RYD_PROTO_LP_SQUARE) || !valid || fabs(q0.xr * q0.xr + q0.xi * q0.xi - 1.0) <= 1e-14;
-  S16_MARK(1);
-  S16_PRIO(3);
-#ifndef RYD_S16_TAIL_PRIO
-#define RYD_S16_TAIL_PRIO 3                  // C3 -1.3 %, C4 unchanged (profiles/r02/ab14)
-#endif
-  // RYD_S16_TAIL_PRIO: in a launch with refill, the last-dispatched round of waves
-  // runs at raised priority so the launch's tail waves finish sooner
-  if (RYD_S16_TAIL_PRIO && !s16_one_round() &&
-      blockIdx.x + 256u * 4u * (unsigned)RYD_S16_WAVES >= gridDim.x)
-    __builtin_amdgcn_s_setprio(RYD_S16_TAIL_PRIO);
-  // states: |11> triangle coordinate r; |01> atom-B coordinate r (r < 5); |00> scalar
-  double t = (r == sym_index(1, 1)) ? 1.0 : 0.0;
-  double z = (r == 1) ? 1.0 : 0.0;
-  double s00 = 1.0;
-  double u[NS];                              // row r of the current propagator
-  double cp = 1.0, sp = 0.0;                 // frame the states are in
-  int nuse = 0, nexec = 0, nsq = 0;        // flop counters (series terms, squarings)
-  bool over_cap = false;
-  const int nseg = n_segments<PROTO>(n_steps);
-  SegRot rw_out = {};                        // LP square: segment 1's lane weights serve the epilogue too
+  constexpr int BAL = PROTO < 0 ? 1 : 0;     // 0, and dependent: the balanced form's statements are discarded
+  constexpr int gpc = 0, nohandoff = 0;
+#include "ryd_sym16_body.inc"
+}
 
-  if constexpr (PROTO == RYD_PROTO_SMOOTH_JP) {
-    // one propagator (every segment has amplitude Omega and duration tau / n_steps),
-    // then n_steps frame-rotated updates.  Phases: lane r computes segment s0 + r of
-    // each 16-segment chunk, the update of segment s0 + j takes it from lane j (DPP).
-    double ph_c, ph_s, dt;
-    double th_c, th_s, dc, ds;               // cos/sin of lane r's modulation angle; chunk step
-    {
-      const PointP& q = q0;
-      dt = q.tau / (double)n_steps;
-      int rep0;
-      int nrep0;
-      build16(u, Ut, q, valid, valid, q.Om, q.Dl, dt, p, r, 0, rep0, nrep0, nuse, nexec, nsq, over_cap,
-              (lds_zero_t*)Zl S16_PROF_PASS);
-      // the modulation angle theta_s = w_mod (s dt + dt/2) - phi_off of segment s = s0 + r
-      // (RG/simulation.py:1698-1731) advances by 16 w_mod dt per chunk: one rotation of
-      // (cos, sin) per chunk instead of a sin/cos evaluation (~1e-15 drift over 19 chunks)
-      fast_sincos(q.wmod * ((double)r * dt + dt / 2) - q.phoff, th_s, th_c);
-      fast_sincos(16.0 * (q.wmod * dt), ds, dc);
-    }
-    const SegRow01 k1 = seg_row01(u, r);
-    const SegRot rw = seg_rot(r);
-    // RYD_JP_WTAB: weight table [point][segment][type 0..4] of (al, be) pairs in Ut; a lane's
-    // type: 0 invariant (1, 0), 1/2 single angle (cr, +-sr), 3/4 double angle (C2, +-S2)
-    d2v* wtab = reinterpret_cast<d2v*>(&Ut[0][0][0]);
-    static_assert(sizeof(Ut) >= sizeof(d2v) * S16_PPW * 16 * 5, "weight table must fit in Ut");
-    const bool th = r == 2 || r == 3 || r == 6 || r == 7 || r == 8 || r == 9;
-    const int wtyp = th ? 1 + (r & 1) : (r == SEG_M || r == SEG_Q) ? 3 + (r & 1) : 0;
-    if constexpr (RYD_JP_WTAB != 0) {
-      wave_sync();                           // the build's transpose reads are done
-      wtab[(p * 16 + r) * 5] = d2v{1.0, 0.0};
-    }
-    for (int s0 = 0; s0 < nseg; s0 += 16) {
-      {
-        const double* pp = prm;
-        asm volatile("" : "+s"(pp));
-        const PointP q = load_point16<PROTO>(pp, ldp, i0, po8);
-        double cth = th_c;
-        if (s0 + 16 > nseg) {                // last chunk: lanes past the end take segment nseg-1
-          double st, ct;
-          fast_sincos(q.wmod * ((double)(nseg - 1) * dt + dt / 2) - q.phoff, st, ct);
-          if (s0 + r >= nseg) cth = ct;
-        }
-        fast_sincos(q.A * cth, ph_s, ph_c);
-        const double tc = fma(th_c, dc, -th_s * ds);
-        th_s = fma(th_s, dc, th_c * ds);
-        th_c = tc;
-      }
-      // lane j: the rotation from segment s0+j-1's frame (lane j-1; lane 0: the frame the
-      // state is in, cp/sp) to segment s0+j's, its double angle -- once per chunk
-      double pc = row_shr1(ph_c), ps = row_shr1(ph_s);
-      if (r == 0) {
-        pc = cp;
-        ps = sp;
-      }
-      const double cr = pc * ph_c + ps * ph_s, sr = ps * ph_c - pc * ph_s;
-      const double C2 = fma(cr, cr, -sr * sr), S2 = 2.0 * (cr * sr);
-      // the frame after this chunk: lane 15 (segment s0+15, or nseg-1 clamped)
-      cp = row_bcast<15>(ph_c);
-      sp = row_bcast<15>(ph_s);
-      if constexpr (RYD_JP_WTAB != 0) {
-        // the rotation weights (al, be) of every lane type for the chunk's 16 segments in
-        // LDS (in Ut, free between the build and the epilogue): lane j writes segment j's
-        // four signed pairs, then each segment costs one 16-byte LDS read per lane instead
-        // of two weight inits and four DPP FMAs
-        wave_sync();                         // the previous chunk's reads are done
-        wtab[(p * 16 + r) * 5 + 1] = d2v{cr, sr};
-        wtab[(p * 16 + r) * 5 + 2] = d2v{cr, -sr};
-        wtab[(p * 16 + r) * 5 + 3] = d2v{C2, S2};
-        wtab[(p * 16 + r) * 5 + 4] = d2v{C2, -S2};
-        wave_sync();
-      }
-      static_for<16>([&](auto J) {
-        constexpr int j = decltype(J)::value;
-        if (s0 + j < nseg) {
-          double al, be;
-          if constexpr (RYD_JP_WTAB != 0) {
-            const d2v w = wtab[(p * 16 + j) * 5 + wtyp];
-            al = w.x;
-            be = w.y;
-          } else {
-            // al = wI + w2 C2_j + wT cr_j, be = b2 S2_j + bT sr_j: row_newbcast operands
-            al = rw.wI;
-            be = 0.0;
-            fmac2_bcast<j>(al, C2, rw.w2, cr, rw.wT);
-            fmac2_bcast<j>(be, S2, rw.b2, sr, rw.bT);
-          }
-          t = fma(al, t, be * quad_swap(t));
-          z = fma(al, z, be * quad_swap(z));
-          seg_apply<false>(u, k1, t, z, s00, (lds_zero_t*)Zl);
-        }
-      });
-    }
-    // |00>: the invariant coordinate is multiplied by the same U'_00 every segment, so
-    // s00 = U'_00^nseg by binary powering (uniform nseg) instead of one multiply per segment
-    {
-      double b = k1.u00, acc = 1.0;
-      for (int e = nseg; e > 0; e >>= 1) {
-        if (e & 1) acc *= b;
-        b *= b;
-      }
-      s00 = acc;
-    }
-  } else {
-    // LP square (2 segments, one propagator when |xi| = 1) and bang-bang (a propagator
-    // per segment).  The states and the frame are parked in LDS across an in-loop
-    // build so that they hold no registers while the Chebyshev series runs.
-    __shared__ double Sv[S16_PPW][16][2];
-    __shared__ double Sp[S16_PPW][8];
-    __shared__ int Sc[S16_PPW][2];
-    constexpr int KEEP = PROTO == RYD_PROTO_LP_SQUARE ? RYD_LP_UNSQUARED : 0;
-    int rep = 0, nrep = 0;                   // unsquared levels of the current propagator
-    SegRow01 k1 = {};                        // the |01> row of the current propagator
-    if (nseg > 0) {
-      // Segment 0 always builds (an all-invalid wave builds identity rows).  The inputs
-      // |11>, |01>, |00> are basis states that every frame rotation leaves alone, so the
-      // first application of U' is a column read: t = U' e_(1,1) (segment-order lane 5),
-      // z = column 1 of the |01> row, s00 = U'_00 -- what seg_apply gives on the unit
-      // vectors (0 * x = 0 for finite rows) without its 20 DPP FMAs and the rotation.
-      const PointP& q = q0;
-      double a, c, sn, dl, dt;
-      bool hold;
-      seg_polar<PROTO>(q, 0, n_steps, frame_ok, a, c, sn, dl, dt, hold);
-      build16(u, Ut, q, valid, valid, a, dl, dt, p, r, KEEP, rep, nrep, nuse, nexec, nsq, over_cap,
-              (lds_zero_t*)Zl S16_PROF_PASS);
-      if constexpr (PROTO != RYD_PROTO_LP_SQUARE) {
-        if (r == 0) {                        // segment the propagator was built for
-          Sp[p][5] = a;
-          Sp[p][6] = dt;
-        }
-      }
-      k1 = seg_row01(u, r);
-      t = u[sym_index(1, 1)];
-      z = k1.o[1];
-      s00 = k1.u00;
-      for (int j = 1; j < (1 << nrep); ++j) {
-        if (j < (1 << rep)) seg_apply(u, k1, t, z, s00);
-      }
-      if (!hold) {
-        cp = c;
-        sp = sn;
-      }
-      wave_sync();
-    }
-    for (int s = 1; s < nseg; ++s) {
-      // re-read the segment's scalars (L1 hits) instead of keeping them live: the
-      // Chebyshev phase needs the registers.  Only what seg_polar reads is loaded here
-      // (LP square: amplitude, duration, xi); a rebuild loads the whole point itself.
-      double a, c, sn, dl, dt;
-      bool hold = false;
-      // LP square with every xi of the wave on the unit circle (or its row invalid): the
-      // segment has segment 0's amplitude and duration (valid: both finite), no rebuild, and
-      // its phase is q0's xi, which stays in registers through the build (LP square has them
-      // to spare: 122 VGPRs) -- no global load, no LDS exchange.  The general path (a non-unit
-      // xi somewhere in the wave; bang-bang always) stays as it was.
-      bool general = true;
-      if constexpr (PROTO == RYD_PROTO_LP_SQUARE) {
-        general = __builtin_amdgcn_ballot_w64(!frame_ok) != 0;
-        c = q0.xr;
-        sn = q0.xi;
-      }
-      if (general) {
-        const double* pp = prm;
-        asm volatile("" : "+s"(pp));
-        const PointP q = load_point16<PROTO>(pp, ldp, i0, po8);
-        seg_polar<PROTO>(q, s, n_steps, frame_ok, a, c, sn, dl, dt, hold);
-        // LP square: segment 0 was built for (Omega, tau), the same loads
-        const bool need = PROTO == RYD_PROTO_LP_SQUARE ? valid && !(a == q.Om && dt == q.tau)
-                                                       : valid && !(a == Sp[p][5] && dt == Sp[p][6]);
-        if (__builtin_amdgcn_ballot_w64(need) != 0) {
-          // Every point of the wave rebuilds: a point whose segment did not change gets
-          // the same propagator bit for bit (its series and squarings do not depend on
-          // its neighbours), so the previous row need not stay live through the build.
-          Sv[p][r][0] = t;
-          Sv[p][r][1] = z;
-          if (r == 0) {
-            Sp[p][0] = s00;
-            Sp[p][1] = cp;
-            Sp[p][2] = sp;
-            Sc[p][0] = nuse;
-            Sc[p][1] = nsq;
-          }
-          int nu = 0, nq = 0;
-          const double* pb = pp;               // bang-bang rebuilds every segment: the same loads
-          if constexpr (PROTO == RYD_PROTO_LP_SQUARE) asm volatile("" : "+s"(pb));   // loaded on this path only
-          const PointP qb = load_point16<PROTO>(pb, ldp, i0, po8);
-          build16(u, Ut, qb, valid, need, a, dl, dt, p, r, KEEP, rep, nrep, nu, nexec, nq, over_cap,
-                  (lds_zero_t*)Zl S16_PROF_PASS);
-          t = Sv[p][r][0];
-          z = Sv[p][r][1];
-          s00 = Sp[p][0];
-          cp = Sp[p][1];
-          sp = Sp[p][2];
-          nuse = Sc[p][0] + nu;
-          nsq = Sc[p][1] + nq;
-          wave_sync();
-          if constexpr (PROTO != RYD_PROTO_LP_SQUARE) {   // LP square has no third segment to compare
-            if (r == 0) {
-              Sp[p][5] = a;
-              Sp[p][6] = dt;
-            }
-            wave_sync();
-          }
-          const double* pq = prm;
-          asm volatile("" : "+s"(pq));
-          seg_polar<PROTO>(load_point16<PROTO>(pq, ldp, i0, po8), s, n_steps, frame_ok, a, c, sn, dl, dt, hold);
-          k1 = seg_row01(u, r);                // the |01> row is not kept live across a build
-        }
-      }
-      if (hold) {
-        c = cp;
-        sn = sp;
-      }
-      const double cr = cp * c + sp * sn, sr = sp * c - cp * sn;
-      rw_out = seg_rot(r);                   // (rotation weights are not kept live across a build)
-      rotate_state(t, z, cr, sr, rw_out);
-      seg_apply(u, k1, t, z, s00);
-      // the unsquared levels: 2^rep - 1 more applications of the built factor, frame fixed
-      for (int j = 1; j < (1 << nrep); ++j) {
-        if (j < (1 << rep)) seg_apply(u, k1, t, z, s00);
-      }
-      cp = c;
-      sp = sn;
-    }
-  }
-  S16_MARK(5);
-  // ---- back to the lab frame Q(cp, sp).  The lane and point indices are recomputed
-  // here (mbcnt, blockIdx) rather than kept live through the series.
-  {
-    const int lid = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    int pl = lid >> 4;
-    asm volatile("" : "+v"(pl));
-    const int64_t b2 = xcd_block(blockIdx.x, gridDim.x);
-    if constexpr (PROTO != RYD_PROTO_LP_SQUARE) rw_out = seg_rot(lid & 15);
-    return sym16_epilogue(t, z, s00, cp, sp, rw_out, valid, over_cap, nuse, nexec, nsq, lid, pl, b2, n, st, lds, sm,
-                          ldm, status, st32 != 0, Ut S16_PROF_PASS);
-  }
+// The balanced form: one workgroup of s16_bal_waves(gpc) waves per gpc groups.
+// Its LDS (a copy of every array per wave and the two handoff slots) keeps one workgroup
+// on a CU, so a launch of at most one workgroup per CU puts gpc groups on each.
+template <int PROTO, int BAL>
+__global__ __launch_bounds__(S16_BLOCK * S16_BAL_MAXW) __attribute__((amdgpu_waves_per_eu(RYD_S16_WAVES, 8))) void
+lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st,
+                      int64_t lds, double* __restrict__ sm, int64_t ldm, uint32_t* __restrict__ status,
+                      int n_steps, int gpc, int st32, int nohandoff) {
+  static_assert(PROTO == RYD_PROTO_LP_SQUARE && BAL == 1, "the balanced form is built for LP square");
+#include "ryd_sym16_body.inc"
 }
 
 __device__ __forceinline__ void sym16_epilogue(double t, double z, double s00, double cp, double sp,
@@ -1249,6 +1124,7 @@ __device__ __forceinline__ void sym16_epilogue(double t, double z, double s00, d
     if (r == 10 || r == 11) v = s16_ts[r - 2];
     if (r == 13) v = (double)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));
     if (r == 14) v = s16_ts[7] - s16_ts[0];
+    if (s16_ts[10] != 0.0 && (r == 12 || r == 15)) v = s16_ts[r == 12 ? 10 : 11];
 #endif
     // the counters: one integer select, then one conversion (the same doubles)
     const int ci = r == 0 ? NS * nuse : r == 1 ? 16 * nexec : nsq;

@@ -218,6 +218,29 @@ def check_coherence_dim(params: np.ndarray, dim: int) -> None:
         raise ValueError("params carry mJ leakage rates (GMJ_A / GMJ_B) that dim=3 would ignore; pass dim=4")
 
 
+def sym16_balance_plan(n: int, cus: int = 256, gpc: int = 0) -> Dict[str, Any]:
+    """The static plan of the sym16 LP-square kernel's CU-balanced launch form for ``n`` points
+    on ``cus`` compute units (``gpc`` > 0 overrides the groups per workgroup): ``groups``,
+    ``workgroups``, ``waves``, ``gpc``, ``auto`` (the automatic rule picks the form) and, per
+    (workgroup, wave), ``role`` (0 whole job, 1 producer, 2 consumer), ``job`` and ``present``.
+    Host code only: no device is touched."""
+    lib = N.load()
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    head = np.zeros(5, dtype=np.int64)
+    need = lib.ryd_sym16_balance_plan(n, cus, gpc, head.ctypes.data_as(i64p), None, None, None, 0)
+    if need < 0:
+        raise ValueError(f"no balanced plan for n={n}, cus={cus}, gpc={gpc}")
+    role = np.zeros(need, dtype=np.int32)
+    job = np.zeros(need, dtype=np.int64)
+    present = np.zeros(need, dtype=np.uint8)
+    lib.ryd_sym16_balance_plan(n, cus, gpc, head.ctypes.data_as(i64p),
+                               role.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), job.ctypes.data_as(i64p),
+                               present.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), need)
+    shape = (int(head[1]), int(head[2]))
+    return dict(groups=int(head[0]), workgroups=shape[0], waves=shape[1], gpc=int(head[3]), auto=bool(head[4]),
+                role=role.reshape(shape), job=job.reshape(shape), present=present.reshape(shape).astype(bool))
+
+
 def device_count() -> int:
     """GPUs visible to the HIP runtime (ryd_device_count)."""
     lib = N.load()

@@ -2,7 +2,12 @@
 (build/libryd_prof.so: shader-clock timestamps written to the summary's unused Lindblad
 columns).  Usage on the GPU box:
     RYD_ENGINE_LIB=$PWD/build/libryd_prof.so python tools/phase_prof.py [c2|c3] [n ...]
+When the launch took the LP-square kernel's CU-balanced form (RYD_S16_BALANCE, ryd_sym16.inc)
+the PROF build also records each wave's role and polls and the producer's stamps: the tool
+then adds the cycles per role, the distribution of wave end times, the consumers that polled
+more than once or fell back, and per workgroup the SIMD every role ran on.
 """
+import os
 import sys
 import warnings
 from collections import defaultdict
@@ -74,3 +79,66 @@ for n in ns:
     if late.any():
         print(f"  waves starting > 2 us after the first: {late.sum()}  (start p50 {np.median(rt0[late]):.2f} us)")
     db.free()
+    code = S[12, ::4]
+    if proto != "lp_square" or not (np.all(code == np.round(code)) and np.any(np.abs(code) >= 1)):
+        continue                             # the one-wave kernel ran: column 12 is AVG_POP
+    # ---- the balanced form: role, workgroup wave index, polls; the producer's stamps
+    pl = E.sym16_balance_plan(n, 256, int(os.environ.get("RYD_S16_BALANCE_GPC", "0")))
+    gpc = pl["gpc"]
+    low = np.mod(code, 64).astype(int)
+    polls = ((code - low) / 64).astype(int)
+    role, wv = (low - 1) % 4, (low - 1) // 4
+    wg = np.zeros(len(code), dtype=int)      # job -> its workgroup (the consumer's entry for a split job)
+    for b, w in zip(*np.nonzero(pl["present"] & (pl["role"] != 1))):
+        wg[pl["job"][b, w]] = b
+    pst = S[15, ::4]
+    pcyc, psimd = np.mod(pst, 1048576.0), (pst // 1048576.0).astype(int)
+    simd_of = (hw >> 4) & 3
+    cu_of = [((int(h) >> 13) & 7, (int(h) >> 12) & 1, (int(h) >> 8) & 15) for h in hw]
+    print(f"== balanced form: gpc {gpc}, {pl['workgroups']} workgroups of {pl['waves']} waves")
+    for rl, nm in ((0, "whole job"), (2, "consumer")):
+        m = role == rl
+        if not m.any():
+            continue
+        print(f"  {nm:9s} waves {m.sum():5d}: " + "  ".join(
+            f"{names[k]} {d[k][m].mean():.0f}" for k in range(6)) + f"  total {tot[m].mean():.0f} (max {tot[m].max():.0f}) cyc")
+    cons = role == 2
+    if cons.any():
+        got = cons & (polls > 0)
+        print(f"  producers (from their consumers' slots): cycles to handoff mean {pcyc[got].mean():.0f} "
+              f"p90 {np.percentile(pcyc[got], 90):.0f} max {pcyc[got].max():.0f}")
+        print(f"  consumers {cons.sum()}: polled once {(cons & (polls == 1)).sum()}, more than once "
+              f"{(cons & (polls > 1)).sum()} (max {polls[cons].max()} polls), fell back {(cons & (polls <= 0)).sum()}")
+        print(f"  consumer wait (its 'cheb' phase, start to columns in hand): mean {d[1][cons].mean():.0f} "
+              f"p90 {np.percentile(d[1][cons], 90):.0f} max {d[1][cons].max():.0f} cyc")
+    pct = [10, 50, 90, 99, 100]
+    print("  wave end times (us after the first start) " + "  ".join(
+        f"p{q} {np.percentile(rt1, q):.2f}" for q in pct))
+    for rl, nm in ((0, "whole job"), (2, "consumer")):
+        if (role == rl).any():
+            print(f"    {nm:9s} end " + "  ".join(f"p{q} {np.percentile(rt1[role == rl], q):.2f}" for q in pct))
+    # placement: per workgroup, the SIMD of each role in wave order; the CU(s) it ran on
+    pat = defaultdict(int)
+    cus = defaultdict(set)
+    lines = []
+    for b in range(pl["workgroups"]):
+        m = np.flatnonzero(wg == b)
+        m = m[np.argsort(wv[m])]
+        wh = [int(simd_of[k]) for k in m if role[k] == 0]
+        co = [int(simd_of[k]) for k in m if role[k] == 2]
+        pr = [int(psimd[k]) if polls[k] > 0 else -1 for k in m if role[k] == 2]
+        where = sorted({cu_of[k] for k in m})
+        for c in where:
+            cus[c].add(b)
+        key = (tuple(wh), tuple(pr), tuple(co))
+        pat[key] += 1
+        lines.append(f"  wg {b:3d} cu {where}: whole {wh} producer {pr} consumer {co}")
+    print(f"  placement patterns (SIMD of whole jobs | producers | consumers, by wave index): {len(pat)} distinct")
+    for key, c in sorted(pat.items(), key=lambda kv: -kv[1])[:8]:
+        print(f"    {c:4d} x  {list(key[0])} | {list(key[1])} | {list(key[2])}")
+    print(f"  (SE, SH, CU) ids seen {len(cus)}; workgroups sharing an id with another: "
+          f"{sum(len(v) > 1 for v in cus.values())} ids (the id does not carry the XCD)")
+    per_simd = np.array([np.bincount([int(simd_of[k]) for k in np.flatnonzero(wg == b)], minlength=4)
+                         for b in range(pl["workgroups"])])
+    print(f"  resident waves per SIMD (whole + consumer), mean over workgroups: {per_simd.mean(axis=0).round(2).tolist()}")
+    print("\n".join(lines))
