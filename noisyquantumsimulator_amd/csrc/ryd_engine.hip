@@ -2426,6 +2426,15 @@ int sym16_balance_mode() {
   const char* e = getenv("RYD_S16_BALANCE");
   return e && e[0] == '0' ? 0 : e && e[0] == '2' ? 2 : 1;
 }
+// RYD_S16_WT: the output stores of the balanced form (S16_WT_* in ryd_sym16.inc) -- 0 plain,
+// 1 the state rows write-through, 3 the summary and status pieces too; unset: automatic (3).
+// Read per launch, so both flavours can alternate in one process.  -1 unset, -2 not a value.
+int sym16_wt_mode() {
+  const char* e = getenv("RYD_S16_WT");
+  if (!e) return -1;
+  if ((e[0] == '0' || e[0] == '1' || e[0] == '3') && e[1] == '\0') return e[0] - '0';
+  return -2;
+}
 int sym16_device_cus() {
   static std::atomic<int> cached[64];
   int dev = 0;
@@ -2685,6 +2694,8 @@ int launch(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, do
     int st32 = sym16_store32_enabled() && lds >= 0 && ldm >= 0 && lds <= (0x1fffffffLL - 15) / 3 &&
                ldm <= (0x1fffffffLL - 3) / 15;
     const int bal = d->protocol == RYD_PROTO_LP_SQUARE ? sym16_balance_mode() : 0;
+    const int wtm = sym16_wt_mode();
+    if (wtm == -2) return fail(RYD_ERR_INVALID, "RYD_S16_WT must be 0, 1 or 3");
     if (bal != 0) {
       // the form is chosen first (forced, or the automatic rule on this device's CU count);
       // the other switches are read, and checked, only by a launch that takes it
@@ -2704,16 +2715,19 @@ int launch(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, do
         const char* eh = getenv("RYD_S16_BALANCE_NOHANDOFF");
         if (pl.workgroups > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
         using BFn = void (*)(const double*, int64_t, int64_t, double*, int64_t, double*, int64_t, uint32_t*,
-                             int, int, int, int);
+                             int, int, int, int, int);
         BFn fb = lindblad_sym16_kernel<RYD_PROTO_LP_SQUARE, 1>;
         int gpc = pl.gpc, noh = eh && eh[0] == '1';
-        void* bargs[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&ds, (void*)&lds, (void*)&dm,
-                         (void*)&ldm, (void*)&dstat, (void*)&ns, (void*)&gpc, (void*)&st32, (void*)&noh};
+        int wt = wtm >= 0 ? wtm : S16_WT_AUTO;
+        void* bargs[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&ds, (void*)&lds, (void*)&dm, (void*)&ldm,
+                         (void*)&dstat, (void*)&ns, (void*)&gpc, (void*)&st32, (void*)&noh, (void*)&wt};
         HIPCHK(hipLaunchKernel((const void*)fb, dim3((unsigned)pl.workgroups), dim3(S16_BLOCK * pl.waves), bargs,
                                0, stream));
         return RYD_OK;
       }
     }
+    // the one-wave kernels have plain stores only: a forced write-through cannot be honoured
+    if (wtm > 0) return fail(RYD_ERR_UNSUPPORTED, "RYD_S16_WT: write-through stores need the balanced launch form");
     void* args[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&ds, (void*)&lds, (void*)&dm,
                     (void*)&ldm, (void*)&dstat, (void*)&ns, (void*)&sh, (void*)&st32};
     HIPCHK(hipLaunchKernel((const void*)f, dim3((unsigned)blocks), dim3(S16_BLOCK), args, 0, stream));

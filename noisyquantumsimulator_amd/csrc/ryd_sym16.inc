@@ -965,7 +965,7 @@ __device__ __forceinline__ void sym16_epilogue(double t, double z, double s00, d
                                                const SegRot& rw, bool valid, bool over_cap, int nuse, int nexec,
                                                int nsq, int l, int p, int64_t blk, int64_t n,
                                                double* __restrict__ st, int64_t lds, double* __restrict__ sm,
-                                               int64_t ldm, uint32_t* __restrict__ status, bool st32,
+                                               int64_t ldm, uint32_t* __restrict__ status, bool st32, int wt,
                                                double (&Ut)[S16_PPW][NS][16] S16_PROF_ARG);
 
 // load_point for a lane of this kernel: column f of the lane's point is read at the
@@ -1002,7 +1002,7 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
                       int n_steps, int shape, int st32) {
   (void)shape;
   constexpr int BAL = PROTO < 0 ? 1 : 0;     // 0, and dependent: the balanced form's statements are discarded
-  constexpr int gpc = 0, nohandoff = 0;
+  constexpr int gpc = 0, nohandoff = 0, wt = 0;
 #include "ryd_sym16_body.inc"
 }
 
@@ -1013,16 +1013,90 @@ template <int PROTO, int BAL>
 __global__ __launch_bounds__(S16_BLOCK * S16_BAL_MAXW) __attribute__((amdgpu_waves_per_eu(RYD_S16_WAVES, 8))) void
 lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st,
                       int64_t lds, double* __restrict__ sm, int64_t ldm, uint32_t* __restrict__ status,
-                      int n_steps, int gpc, int st32, int nohandoff) {
+                      int n_steps, int gpc, int st32, int nohandoff, int wt) {
   static_assert(PROTO == RYD_PROTO_LP_SQUARE && BAL == 1, "the balanced form is built for LP square");
 #include "ryd_sym16_body.inc"
+}
+
+// Output stores of the balanced form (`wt`, a kernel argument: RYD_S16_WT in launch()).  A
+// one-round launch ends everywhere at once: with plain stores the 956 bytes per point sit
+// dirty in the XCDs' L2s until the end-of-kernel release writes them back while nothing else
+// runs.  A write-through store (relaxed, agent scope: global_store ... sc1) sends its line on
+// to memory as it is issued, while other waves still compute, and the release finds the L2s
+// clean.  The same values at the same addresses either way.  C2, kernel time: plain 25.96 us,
+// the state rows write-through 25.09, the 32-byte summary and status pieces too 24.77 (four
+// partial writes per line instead of one merged in L2 still cost less than leaving the line
+// for the release): profiles/sym16_edges/.
+constexpr int S16_WT_STATE = 1, S16_WT_SUMMARY = 2;
+constexpr int S16_WT_AUTO = S16_WT_STATE | S16_WT_SUMMARY;   // launch() without RYD_S16_WT
+template <bool WT, typename P, typename T>
+__device__ __forceinline__ void s16_store(P* ptr, T v) {
+  if constexpr (WT) __hip_atomic_store(ptr, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else *ptr = v;
+}
+
+// the 25 state rows of a wave's four points: lane l stores column cc of rows l / 16 + 4 j
+template <bool WT>
+__device__ __forceinline__ void s16_store_state(const double (&v)[7], double* __restrict__ st, int64_t lds,
+                                                int64_t i0, int l, int cc, bool in, bool st32) {
+  if (st32) {
+    // the wave-uniform address st + 4 i0 + 4 j lds (SGPRs) plus the lane's 32-bit byte
+    // offset 8 (cc + (l / 16) lds); launch() has checked that the offset fits
+    const unsigned lo = 8u * ((unsigned)cc + (unsigned)(l >> 4) * (unsigned)lds);
+    if (in) {
+#pragma unroll
+      for (int j = 0; j < 7; ++j) {
+        if (j < 6 || l < 16) {
+          char* bj = reinterpret_cast<char*>(st + (4 * i0 + 4 * j * lds));
+          asm("" : "+s"(bj));
+          s16_store<WT>(reinterpret_cast<s16_gdouble*>((s16_gchar*)bj + lo), v[j]);
+        }
+      }
+    }
+  } else {
+    double* dst = st + 4 * i0 + cc;
+    if (in) {
+#pragma unroll
+      for (int j = 0; j < 7; ++j) {
+        const int row = (l >> 4) + 4 * j;
+        if (j < 6 || l < 16) s16_store<WT>(dst + (int64_t)row * lds, v[j]);
+      }
+    }
+  }
+}
+
+// lane r's summary column of point i = i0 + p, the counters (lanes 0-3) and the status word
+template <bool WT>
+__device__ __forceinline__ void s16_store_summary(double v, double c, uint32_t stat, double* __restrict__ sm,
+                                                  int64_t ldm, uint32_t* __restrict__ status, int64_t i0, int64_t i,
+                                                  int r, int p, bool st32) {
+  if (st32) {
+    // the point is i0 + p.  Wave-uniform bases sm + i0, sm + 16 ldm + i0 and status + i0 plus
+    // the lane's 32-bit byte offsets (checked by launch())
+    char* b0 = reinterpret_cast<char*>(sm + i0);
+    char* b1 = reinterpret_cast<char*>(sm + (RYD_S_NMV_USEFUL * ldm + i0));
+    char* b2 = reinterpret_cast<char*>(status + i0);
+    asm("" : "+s"(b0));
+    asm("" : "+s"(b1));
+    asm("" : "+s"(b2));
+    const unsigned lo = 8u * ((unsigned)r * (unsigned)ldm + (unsigned)p);
+    s16_store<WT>(reinterpret_cast<s16_gdouble*>((s16_gchar*)b0 + lo), v);
+    if (r < 4) s16_store<WT>(reinterpret_cast<s16_gdouble*>((s16_gchar*)b1 + lo), c);
+    if (r == 0)
+      s16_store<WT>(reinterpret_cast<__attribute__((address_space(1))) uint32_t*>((s16_gchar*)b2 + 4u * (unsigned)p),
+                    stat);
+  } else {
+    s16_store<WT>(sm + ((int64_t)r * ldm + i), v);
+    if (r < 4) s16_store<WT>(sm + ((int64_t)(RYD_S_NMV_USEFUL + r) * ldm + i), c);
+    if (r == 0) s16_store<WT>(status + i, stat);
+  }
 }
 
 __device__ __forceinline__ void sym16_epilogue(double t, double z, double s00, double cp, double sp,
                                                const SegRot& rw, bool valid, bool over_cap, int nuse, int nexec,
                                                int nsq, int l, int p, int64_t blk, int64_t n,
                                                double* __restrict__ st, int64_t lds, double* __restrict__ sm,
-                                               int64_t ldm, uint32_t* __restrict__ status, bool st32,
+                                               int64_t ldm, uint32_t* __restrict__ status, bool st32, int wt,
                                                double (&Ut)[S16_PPW][NS][16] S16_PROF_ARG) {
   const int r = l & 15;
   const bool lane_ok = r < NS;
@@ -1067,30 +1141,10 @@ __device__ __forceinline__ void sym16_epilogue(double t, double z, double s00, d
     for (int j = 0; j < 7; ++j)              // rows 25 .. 27 (j = 6, lanes >= 16): read inside Ut, never stored
       v[j] = (&Ro[pp][k][0])[(l >> 4) + 4 * j];
     static_assert(NC == 25, "rows l/16 + 4 j: j < 6 always inside, j = 6 on the first 16 lanes only");
-    if (st32) {
-      // the wave-uniform address st + 4 i0 + 4 j lds (SGPRs) plus the lane's 32-bit byte
-      // offset 8 (cc + (l / 16) lds); launch() has checked that the offset fits
-      const unsigned lo = 8u * ((unsigned)cc + (unsigned)(l >> 4) * (unsigned)lds);
-      if (in) {
-#pragma unroll
-        for (int j = 0; j < 7; ++j) {
-          if (j < 6 || l < 16) {
-            char* bj = reinterpret_cast<char*>(st + (4 * i0 + 4 * j * lds));
-            asm("" : "+s"(bj));
-            *reinterpret_cast<s16_gdouble*>((s16_gchar*)bj + lo) = v[j];
-          }
-        }
-      }
-    } else {
-      double* dst = st + 4 * i0 + cc;
-      if (in) {
-#pragma unroll
-        for (int j = 0; j < 7; ++j) {
-          const int row = (l >> 4) + 4 * j;
-          if (j < 6 || l < 16) dst[(int64_t)row * lds] = v[j];
-        }
-      }
-    }
+#ifndef RYD_S16_PROBE_NOSTATE                // timing-only probe build: no state stores, wrong results
+    if (wt & S16_WT_STATE) s16_store_state<true>(v, st, lds, i0, l, cc, in, st32);
+    else s16_store_state<false>(v, st, lds, i0, l, cc, in, st32);
+#endif
   }
 #ifdef RYD_S16_PROF
   S16_MARK(7);
@@ -1128,28 +1182,16 @@ __device__ __forceinline__ void sym16_epilogue(double t, double z, double s00, d
 #endif
     // the counters: one integer select, then one conversion (the same doubles)
     const int ci = r == 0 ? NS * nuse : r == 1 ? 16 * nexec : nsq;
-    const double c = r == 2 ? tr11 : (double)ci;
+    double c = r == 2 ? tr11 : (double)ci;
+#ifdef RYD_S16_PROF
+    // the start-up stamps in place of three counters: barrier passed, column loads issued,
+    // values in hand (cycles from entry; 'load' ends at column 4)
+    if (r >= 1 && r < 4) c = s16_ts[11 + r] - s16_ts[0];
+#endif
     uint32_t stat = valid ? 0u : RYD_STATUS_BAD_INPUT;
     if (over_cap) stat |= RYD_STATUS_STEP_CAP;
     if (!fin) stat |= RYD_STATUS_NONFINITE;
-    if (st32) {
-      // ip < n: the point is i0 + p.  Wave-uniform bases sm + i0, sm + 16 ldm + i0 and
-      // status + i0 plus the lane's 32-bit byte offsets (checked by launch())
-      char* b0 = reinterpret_cast<char*>(sm + i0);
-      char* b1 = reinterpret_cast<char*>(sm + (RYD_S_NMV_USEFUL * ldm + i0));
-      char* b2 = reinterpret_cast<char*>(status + i0);
-      asm("" : "+s"(b0));
-      asm("" : "+s"(b1));
-      asm("" : "+s"(b2));
-      const unsigned lo = 8u * ((unsigned)r * (unsigned)ldm + (unsigned)p);
-      *reinterpret_cast<s16_gdouble*>((s16_gchar*)b0 + lo) = v;
-      if (r < 4) *reinterpret_cast<s16_gdouble*>((s16_gchar*)b1 + lo) = c;
-      if (r == 0)
-        *reinterpret_cast<__attribute__((address_space(1))) uint32_t*>((s16_gchar*)b2 + 4u * (unsigned)p) = stat;
-    } else {
-      sm[(int64_t)r * ldm + i] = v;
-      if (r < 4) sm[(int64_t)(RYD_S_NMV_USEFUL + r) * ldm + i] = c;
-      if (r == 0) status[i] = stat;
-    }
+    if (wt & S16_WT_SUMMARY) s16_store_summary<true>(v, c, stat, sm, ldm, status, i0, i, r, p, st32);
+    else s16_store_summary<false>(v, c, stat, sm, ldm, status, i0, i, r, p, st32);
   }
 }

@@ -4,16 +4,17 @@
 // kernel parameters, and
 //   BAL = 0: one wave per workgroup, one job (the three one-wave kernels);
 //   BAL = 1: a wave of the balanced form's workgroup (LP square; `gpc` groups per workgroup,
-//            `nohandoff`): every LDS array gets a copy per wave, the job comes from the role
+//            `nohandoff`, `wt`): every LDS array gets a copy per wave, the job comes from the role
 //            table, and the first build may be split with a partner wave (build16<S16Handoff>).
   constexpr int NW = BAL ? S16_BAL_MAXW : 1;
   __shared__ __attribute__((aligned(16))) double UtW[NW][S16_PPW][NS][16];   // transpose, then output staging
   static_assert(sizeof(UtW[0]) >= sizeof(double) * S16_PPW * 4 * NC, "output staging must fit in Ut");
 #ifdef RYD_S16_PROF
-  double s16_ts[12];
+  double s16_ts[16];
   s16_ts[8] = (double)__builtin_amdgcn_s_memrealtime();
   S16_MARK(0);
   s16_ts[10] = s16_ts[11] = 0.0;             // balanced form: role and handoff record
+  s16_ts[12] = 0.0;                          // balanced form: the barrier's stamp
   int bal_polls = 0;
 #endif
   __shared__ double ZlW[NW][16];             // zero words: squaring accumulator clears, lane 15's row
@@ -33,9 +34,13 @@
     role = s16_bal_role(gpc, wv);
     job = s16_bal_job(blockIdx.x, gridDim.x, role.off);
     // the flags start clear in every launch (LDS keeps what the last workgroup left): the
-    // one workgroup barrier of the kernel, before the roles part ways
+    // one workgroup barrier of the kernel, before the roles part ways.  (Requesting the
+    // parameter columns before it, with every kernel argument fetched at entry, shortens the
+    // start-up by 0.05 us and lengthens the launch by 0.4 us: the barrier waits for the
+    // workgroup's last-dispatched wave, not for memory -- profiles/sym16_edges/.)
     if (threadIdx.x < 2) Hflag[threadIdx.x] = 0;
     __syncthreads();
+    S16_MARK(12);
     // a job past the batch: its producer and its consumer both leave here, by the same test
     if (job >= (n + S16_PPW - 1) / S16_PPW) return;
     if (role.role != S16_BAL_WHOLE) __builtin_amdgcn_s_setprio(3);   // both halves of a split job: see s16_phase_prio
@@ -48,6 +53,11 @@
   const unsigned po8 = 8u * (unsigned)min(p, last < S16_PPW - 1 ? (int)last : S16_PPW - 1);
   // loaded and validated once; the segment-0 build takes its inputs from here
   const PointP q0 = load_point16<PROTO>(prm, ldp, i0, po8);
+  S16_MARK(13);
+#ifdef RYD_S16_PROF
+  asm volatile("s_waitcnt vmcnt(0)" ::"v"(q0.Om), "v"(q0.xi) : "memory");   // the stamp of "values in hand"
+  S16_MARK(14);
+#endif
   const bool valid = point_valid<PROTO>(q0, n_steps);
   const bool frame_ok =
       !(PROTO == RYD_PROTO_LP_SQUARE) || !valid || fabs(q0.xr * q0.xr + q0.xi * q0.xi - 1.0) <= 1e-14;
@@ -335,5 +345,5 @@
     }
 #endif
     return sym16_epilogue(t, z, s00, cp, sp, rw_out, valid, over_cap, nuse, nexec, nsq, lid, pl, b2, n, st, lds, sm,
-                          ldm, status, st32 != 0, Ut S16_PROF_PASS);
+                          ldm, status, st32 != 0, wt, Ut S16_PROF_PASS);
   }

@@ -6,6 +6,10 @@ When the launch took the LP-square kernel's CU-balanced form (RYD_S16_BALANCE, r
 the PROF build also records each wave's role and polls and the producer's stamps: the tool
 then adds the cycles per role, the distribution of wave end times, the consumers that polled
 more than once or fell back, and per workgroup the SIMD every role ran on.
+For both forms the 'load' phase is split at the PROF build's start-up stamps (the workgroup
+barrier passed, the parameter column loads issued, their values in hand), and the waves' span
+from the first start to the last end is set against the kernel's time: what is left is
+dispatch before the first wave and drain after the last.
 """
 import os
 import sys
@@ -49,6 +53,26 @@ for n in ns:
     for k, nm in enumerate(names):
         print(f"  {nm:10s} mean {d[k].mean():9.0f} cyc  p10 {np.percentile(d[k], 10):9.0f}  "
               f"p90 {np.percentile(d[k], 90):9.0f}  max {d[k].max():9.0f}")
+    # the start-up in four parts (the PROF build's extra stamps, cycles from entry, in the
+    # counter columns 17-19): the barrier (balanced form only) and the issue of the column
+    # loads come in either order, values in hand = the first s_waitcnt vmcnt(0) returned
+    bar, iss, hand = S[17, ::4], S[18, ::4], S[19, ::4]
+    def dist(nm, x):
+        print(f"    {nm:38s} mean {x.mean():7.0f} cyc  p10 {np.percentile(x, 10):7.0f}  p90 "
+              f"{np.percentile(x, 90):7.0f}  max {x.max():7.0f}")
+    print("  'load' in parts:")
+    if np.all(bar > 0) and np.all(bar <= iss):                   # barrier first
+        dist("entry -> barrier passed", bar)
+        dist("barrier passed -> column loads issued", iss - bar)
+        dist("column loads issued -> values in hand", hand - iss)
+    elif np.all(bar > 0):                                        # loads first
+        dist("entry -> column loads issued", iss)
+        dist("column loads issued -> barrier passed", bar - iss)
+        dist("barrier passed -> values in hand", hand - bar)
+    else:                                                        # one-wave kernel: no barrier
+        dist("entry -> column loads issued", iss)
+        dist("column loads issued -> values in hand", hand - iss)
+    dist("values in hand -> point_valid done", cyc[0] - hand)
     print(f"  (epilogue: rotate + LDS staging + state stores {stage.mean():.0f} cyc, summary "
           f"{(cyc[5] - S[14, ::4]).mean():.0f} cyc)")
     tot = cyc[-1]
@@ -57,6 +81,9 @@ for n in ns:
     rt1 = (t1 - t0.min()) * 0.01
     print(f"  wall: start p50 {np.median(rt0):.2f} us max {rt0.max():.2f}; end p50 {np.median(rt1):.2f} "
           f"max {rt1.max():.2f}; wave duration p50 {np.median(rt1 - rt0):.2f} us max {(rt1 - rt0).max():.2f}")
+    span = rt1.max()
+    print(f"  wave span (first start to last end) {span:.2f} us of the kernel's {ms * 1e3:.2f} us: "
+          f"{ms * 1e3 - span:.2f} us outside the waves")
     print(f"  clock: {np.median(tot / np.maximum(rt1 - rt0, 1e-3)) / 1e3:.2f} GHz (cycles / wall)")
     simd = defaultdict(list)
     for k in range(len(hw)):
