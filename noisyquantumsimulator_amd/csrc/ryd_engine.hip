@@ -2396,6 +2396,14 @@ bool sym16_store32_enabled() {
   return !(e && e[0] == '1');
 }
 
+// RYD_S16_PARAM64=1 makes the balanced sym16 kernel load its parameter columns one by one
+// at 64-bit column addresses for every launch (the form it takes anyway when 8 (14 ld_params
+// + n) does not fit 31 bits): tests run both
+bool sym16_param32_enabled() {
+  const char* e = getenv("RYD_S16_PARAM64");
+  return !(e && e[0] == '1');
+}
+
 // The balanced launch form of the sym16 LP-square kernel (ryd_sym16.inc): the static plan
 // for n points on `cus` compute units.  gpc_override > 0 sets the groups per workgroup.
 // auto_on: the launches the form is measured to win -- every wave resident at once, more
@@ -2716,7 +2724,12 @@ int launch(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, do
         if (pl.workgroups > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
         using BFn = void (*)(const double*, int64_t, int64_t, double*, int64_t, double*, int64_t, uint32_t*,
                              int, int, int, int, int);
-        BFn fb = lindblad_sym16_kernel<RYD_PROTO_LP_SQUARE, 1>;
+        // the first parameter load is one instruction per wave (load_point16_row) where its
+        // largest 32-bit lane offset, 8 (14 ldp + n), fits 31 bits: LP square reads columns
+        // 0 .. RYD_P_XI_IM = 14
+        static_assert(RYD_P_XI_IM == 14, "the largest LP-square parameter column");
+        const bool p32 = sym16_param32_enabled() && ldp <= (0x7fffffffLL / 8 - n) / 14;
+        BFn fb = p32 ? lindblad_sym16_kernel<RYD_PROTO_LP_SQUARE, 2> : lindblad_sym16_kernel<RYD_PROTO_LP_SQUARE, 1>;
         int gpc = pl.gpc, noh = eh && eh[0] == '1';
         int wt = wtm >= 0 ? wtm : S16_WT_AUTO;
         void* bargs[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&ds, (void*)&lds, (void*)&dm, (void*)&ldm,

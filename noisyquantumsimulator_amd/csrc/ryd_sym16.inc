@@ -995,6 +995,54 @@ __device__ __forceinline__ PointP load_point16(const double* __restrict__ prm, i
   return q;
 }
 
+// The balanced form's first load where launch() has checked that 8 (14 ldp + n) fits 31 bits
+// (BAL = 2): ONE load instruction per wave.  Lane r of a row loads column r of the row's
+// point (lane 15 repeats column 14) at the wave-uniform base prm + i0 plus its 32-bit byte
+// offset 8 r ldp + po8, and the row's 15 values go to all its lanes by DPP row broadcasts
+// (moves: the same doubles as 15 loads of 16 equal addresses each).  A one-round launch has
+// every wave of a CU at this point at once, and the CU's one address unit takes a 64-lane load
+// at a time: 15 per wave kept it busy for ~2900 cycles, the start-up of the last wave served
+// (profiles/sym16_start/).  The 64-bit form (load_point16) stays for batches beyond the check
+// and under RYD_S16_PARAM64=1, and for the rare reloads of the general path.
+template <int PROTO>
+__device__ __forceinline__ PointP load_point16_row(const double* __restrict__ prm, int64_t ldp, int64_t i0,
+                                                   unsigned po8, int r) {
+  static_assert(PROTO == RYD_PROTO_LP_SQUARE && RYD_P_XI_IM == NS - 1, "LP square: columns 0 .. 14, one per lane");
+  const unsigned f = (unsigned)(r < NS ? r : NS - 1);
+  const unsigned off = f * (8u * (unsigned)ldp) + po8;
+  const char* base = reinterpret_cast<const char*>(prm + i0);
+  asm("" : "+s"(base));                      // stays a scalar base (load_point16)
+  const double x = *reinterpret_cast<const s16_gdouble*>((const s16_gchar*)base + off);
+  double c[NS];
+  static_for<NS>([&](auto K) { c[decltype(K)::value] = row_bcast<decltype(K)::value>(x); });
+  PointP q = load_point_with<PROTO>([&](int k) { return c[k]; });
+  q.prm = prm;
+  q.ld = ldp;
+  q.i = i0 + (int64_t)(po8 >> 3);
+  return q;
+}
+
+// The balanced form's validity test of its first load: the loaded columns are taken in hand at
+// one point (a single wait for the last of them instead of one per column as each is first
+// compared), and point_valid's predicates are ANDed without its short-circuit order, which the
+// compiler turns into nested exec-masked blocks.  Every predicate is a pure compare, so the
+// result is point_valid's for every input, NaNs and negative values included.
+__device__ __forceinline__ void s16_in_hand(PointP& q) {
+  asm volatile("" : "+v"(q.Om), "+v"(q.Dl), "+v"(q.V), "+v"(q.d1), "+v"(q.gA[0]), "+v"(q.gA[1]), "+v"(q.gA[2]),
+               "+v"(q.gA[3]), "+v"(q.gB[0]), "+v"(q.gB[1]), "+v"(q.gB[2]), "+v"(q.gB[3]), "+v"(q.tau), "+v"(q.xr),
+               "+v"(q.xi));
+}
+template <int PROTO>
+__device__ __forceinline__ bool point_valid_flat(const PointP& q) {
+  static_assert(PROTO == RYD_PROTO_LP_SQUARE, "point_valid's LP-square predicates");
+  const auto fin = [](double x) { return (int)isfinite(x); };
+  int ok = (int)(q.Om > 0.0) & fin(q.Om) & fin(q.V) & fin(q.Dl) & fin(q.d1);
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+    ok &= (int)(q.gA[c] >= 0.0) & (int)(q.gB[c] >= 0.0) & fin(q.gA[c]) & fin(q.gB[c]);
+  return (ok & (int)(q.tau > 0.0) & fin(q.tau)) != 0;
+}
+
 template <int PROTO>
 __global__ __launch_bounds__(S16_BLOCK) __attribute__((amdgpu_waves_per_eu(PROTO == RYD_PROTO_BANGBANG ? 3 : RYD_S16_WAVES, 8))) void
 lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st,
@@ -1002,19 +1050,24 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
                       int n_steps, int shape, int st32) {
   (void)shape;
   constexpr int BAL = PROTO < 0 ? 1 : 0;     // 0, and dependent: the balanced form's statements are discarded
-  constexpr int gpc = 0, nohandoff = 0, wt = 0;
+  constexpr int gpc = 0, nohandoff = 0, wt = 0, p32 = 0;
 #include "ryd_sym16_body.inc"
 }
 
 // The balanced form: one workgroup of s16_bal_waves(gpc) waves per gpc groups.
 // Its LDS (a copy of every array per wave and the two handoff slots) keeps one workgroup
 // on a CU, so a launch of at most one workgroup per CU puts gpc groups on each.
+// BAL = 2: the first load is one instruction with 32-bit lane offsets (load_point16_row; launch()
+// picks it where the offsets fit).  A template argument, not a kernel argument: behind a
+// run-time branch the compiler merges the two forms' loads and gives every column a per-lane
+// 64-bit address.
 template <int PROTO, int BAL>
 __global__ __launch_bounds__(S16_BLOCK * S16_BAL_MAXW) __attribute__((amdgpu_waves_per_eu(RYD_S16_WAVES, 8))) void
 lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st,
                       int64_t lds, double* __restrict__ sm, int64_t ldm, uint32_t* __restrict__ status,
                       int n_steps, int gpc, int st32, int nohandoff, int wt) {
-  static_assert(PROTO == RYD_PROTO_LP_SQUARE && BAL == 1, "the balanced form is built for LP square");
+  static_assert(PROTO == RYD_PROTO_LP_SQUARE && (BAL == 1 || BAL == 2), "the balanced form is built for LP square");
+  constexpr int p32 = BAL == 2;
 #include "ryd_sym16_body.inc"
 }
 

@@ -5,7 +5,9 @@
 //   BAL = 0: one wave per workgroup, one job (the three one-wave kernels);
 //   BAL = 1: a wave of the balanced form's workgroup (LP square; `gpc` groups per workgroup,
 //            `nohandoff`, `wt`): every LDS array gets a copy per wave, the job comes from the role
-//            table, and the first build may be split with a partner wave (build16<S16Handoff>).
+//            table, and the first build may be split with a partner wave (build16<S16Handoff>);
+//   BAL = 2: the same, with `p32`: the first parameter load is one instruction per wave
+//            (load_point16_row).  Both take the branch-free validity test (point_valid_flat).
   constexpr int NW = BAL ? S16_BAL_MAXW : 1;
   __shared__ __attribute__((aligned(16))) double UtW[NW][S16_PPW][NS][16];   // transpose, then output staging
   static_assert(sizeof(UtW[0]) >= sizeof(double) * S16_PPW * 4 * NC, "output staging must fit in Ut");
@@ -52,13 +54,22 @@
   const int64_t last = n - 1 - i0;           // >= 0
   const unsigned po8 = 8u * (unsigned)min(p, last < S16_PPW - 1 ? (int)last : S16_PPW - 1);
   // loaded and validated once; the segment-0 build takes its inputs from here
-  const PointP q0 = load_point16<PROTO>(prm, ldp, i0, po8);
+  PointP q0l;
+  if constexpr (p32 != 0) {
+    q0l = load_point16_row<PROTO>(prm, ldp, i0, po8, r);
+  } else {
+    q0l = load_point16<PROTO>(prm, ldp, i0, po8);
+  }
   S16_MARK(13);
+  if constexpr (BAL != 0) s16_in_hand(q0l);
+  const PointP q0 = q0l;
 #ifdef RYD_S16_PROF
   asm volatile("s_waitcnt vmcnt(0)" ::"v"(q0.Om), "v"(q0.xi) : "memory");   // the stamp of "values in hand"
   S16_MARK(14);
 #endif
-  const bool valid = point_valid<PROTO>(q0, n_steps);
+  bool valid;
+  if constexpr (BAL != 0) valid = point_valid_flat<PROTO>(q0);
+  else valid = point_valid<PROTO>(q0, n_steps);
   const bool frame_ok =
       !(PROTO == RYD_PROTO_LP_SQUARE) || !valid || fabs(q0.xr * q0.xr + q0.xi * q0.xi - 1.0) <= 1e-14;
   S16_MARK(1);
