@@ -35,6 +35,16 @@
  * drive never couples |r->, and no jump creates an |r-> coherence, so this is again
  * the exact invariant sector); ket rows are 16 complex amplitudes, basis 4*a1 + a2.
  *
+ * Summary-only runs: the state pointer of ryd_run_batch (out_state) and of
+ * ryd_run_batch_device (d_state) may be NULL.  ld_state is then ignored, no state row is
+ * written, copied or staged anywhere the caller can see, and summary, status and ryd_stats
+ * are those of the full call bit for bit.  The default dim-3 identical-atom Lindblad kernel
+ * of LP square, bang-bang and smooth JP and the ket block kernel (dim 3 and 4) have store-free
+ * twins for this; every other descriptor (shaped LP and dim-4 Lindblad among them) runs its
+ * ordinary kernel into a scratch buffer from the library's private stream-ordered pool,
+ * freed on the stream.  RYD_NOSTATE=0 (environment, read per launch) sends every
+ * summary-only launch down that scratch-buffer path (A/B measurements, cross-checks).
+ *
  * Ownership/threading: the caller owns every buffer; the library never keeps a
  * pointer after return (device-buffer calls: until the stream work completes).
  * One handle per host thread.  Errors: negative return + ryd_last_error()
@@ -302,7 +312,9 @@ int ryd_create(const int* device_ids, int n_devices, ryd_handle** out);
 int ryd_destroy(ryd_handle* h);
 
 /* Host buffers in/out; range-partitions the points over the handle's devices
- * (one stream each, no inter-device communication), blocks until done. */
+ * (one stream each, no inter-device communication), blocks until done.
+ * out_state may be NULL (summary-only, see the data layout above): the device workspace,
+ * the pinned staging, the D2H and the unpack then carry the summary and status alone. */
 int ryd_run_batch(ryd_handle* h, const ryd_batch_desc* desc,
                   const double* params, int64_t n, int64_t ld_params,
                   double* out_state, int64_t ld_state,
@@ -312,7 +324,8 @@ int ryd_run_batch(ryd_handle* h, const ryd_batch_desc* desc,
 /* Device buffers already resident on device slot `slot`; enqueues on `stream`
  * (hipStream_t, NULL = the handle's stream for that slot) and returns.
  * If `elapsed_ms` is non-NULL the call records HIP events around the launch on
- * that stream, waits, and reports the kernel's device time. */
+ * that stream, waits, and reports the kernel's device time.
+ * d_state may be NULL (summary-only): ld_state is ignored. */
 int ryd_run_batch_device(ryd_handle* h, int slot, const ryd_batch_desc* desc,
                          const double* d_params, int64_t n, int64_t ld_params,
                          double* d_state, int64_t ld_state,

@@ -157,6 +157,7 @@ def load() -> ctypes.CDLL:
         lib.ryd_device_count.argtypes = [ctypes.POINTER(ctypes.c_int)]
         lib.ryd_create.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(vp)]
         lib.ryd_destroy.argtypes = [vp]
+        # the state pointer of both forms may be None (NULL): a summary-only run
         lib.ryd_run_batch.argtypes = [vp, ctypes.POINTER(BatchDesc), dp, i64, i64, dp, i64, dp, i64,
                                       ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(Stats)]
         lib.ryd_run_batch_device.argtypes = [vp, ctypes.c_int, ctypes.POINTER(BatchDesc), vp, i64, i64,

@@ -904,150 +904,17 @@ template <int PROTO, int KD>
 __global__ __launch_bounds__(BLOCK) void ket_block_kernel(
     const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st, int64_t lds,
     double* __restrict__ sm, int64_t ldm, uint32_t* __restrict__ status, int n_steps, int shape) {
-  const int64_t gi = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (gi >= n) return;
-  const int64_t i = gi;
-  const PointP q = load_point<PROTO>(prm, ldp, i);
-  const bool valid = point_valid<PROTO>(q, n_steps);
-  // |01> block (c01, c0r) and the |11> symmetric block (c11, c+, crr), complex
-  double b2r[2] = {1.0, 0.0}, b2i[2] = {0.0, 0.0};
-  double b3r[3] = {1.0, 0.0, 0.0}, b3i[3] = {0.0, 0.0, 0.0};
-  KetBlocks K;
-  K.a = K.dl = K.dt = -1.0;                  // nothing built yet
-  bool over_cap = false;
-  int nseg_used = 0, nbuild = 0;
-  const int nseg = n_segments<PROTO>(n_steps);
-  for (int s = 0; s < nseg && valid; ++s) {
-    double a, c, sn, dl, dt;
-    ket_seg_polar<PROTO>(q, s, n_steps, shape, a, c, sn, dl, dt);
-    if (!(dt > 0.0)) continue;               // empty / padding segment: identity
-    {                                        // the ket_cheb_kernel's step cap, same bound
-      Seg g;
-      g.om_re = a;
-      g.om_im = 0.0;
-      g.dl = dl;
-      g.dt = dt;
-      double emin, emax;
-      h_bounds(g, q.V, q.d1, emin, emax);
-      if (!(0.5 * (emax - emin) * dt <= X_CAP)) {
-        over_cap = true;
-        continue;
-      }
-    }
-    if (!(a == K.a && dl == K.dl && dt == K.dt)) {
-      ket_blocks_build(K, a, dl, dt, q.d1, q.V);
-      ++nbuild;
-    }
-    ++nseg_used;
-    // frame: w = D^dag b, w <- U w, b = D w  (D = diag(1, e^{i phi}[, e^{2 i phi}]))
-    const double c2 = fma(c, c, -sn * sn), s2 = 2.0 * c * sn;
-    {
-      const double xr = CMUL_RE(b2r[1], b2i[1], c, -sn), xi = CMUL_IM(b2r[1], b2i[1], c, -sn);
-      const double yr = CMUL_RE(K.u2[0][0], K.u2[0][1], b2r[0], b2i[0]) +
-                        CMUL_RE(K.u2[1][0], K.u2[1][1], xr, xi);
-      const double yi = CMUL_IM(K.u2[0][0], K.u2[0][1], b2r[0], b2i[0]) +
-                        CMUL_IM(K.u2[1][0], K.u2[1][1], xr, xi);
-      const double zr = CMUL_RE(K.u2[1][0], K.u2[1][1], b2r[0], b2i[0]) +
-                        CMUL_RE(K.u2[2][0], K.u2[2][1], xr, xi);
-      const double zi = CMUL_IM(K.u2[1][0], K.u2[1][1], b2r[0], b2i[0]) +
-                        CMUL_IM(K.u2[2][0], K.u2[2][1], xr, xi);
-      b2r[0] = yr;
-      b2i[0] = yi;
-      b2r[1] = CMUL_RE(zr, zi, c, sn);
-      b2i[1] = CMUL_IM(zr, zi, c, sn);
-    }
-    {
-      const double wr[3] = {b3r[0], CMUL_RE(b3r[1], b3i[1], c, -sn), CMUL_RE(b3r[2], b3i[2], c2, -s2)};
-      const double wi[3] = {b3i[0], CMUL_IM(b3r[1], b3i[1], c, -sn), CMUL_IM(b3r[2], b3i[2], c2, -s2)};
-      const int U[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
-      double yr[3], yi[3];
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        double accr = 0.0, acci = 0.0;
-#pragma unroll
-        for (int m = 0; m < 3; ++m) {
-          const double ur = K.u3[U[r][m]][0], ui = K.u3[U[r][m]][1];
-          accr = fma(ur, wr[m], fma(-ui, wi[m], accr));
-          acci = fma(ur, wi[m], fma(ui, wr[m], acci));
-        }
-        yr[r] = accr;
-        yi[r] = acci;
-      }
-      b3r[0] = yr[0];
-      b3i[0] = yi[0];
-      b3r[1] = CMUL_RE(yr[1], yi[1], c, sn);
-      b3i[1] = CMUL_IM(yr[1], yi[1], c, sn);
-      b3r[2] = CMUL_RE(yr[2], yi[2], c2, s2);
-      b3i[2] = CMUL_IM(yr[2], yi[2], c2, s2);
-    }
-  }
-  // rows of the ket layout (2 D doubles per input, D = KD^2, basis KD*a1 + a2; |r-> rows
-  // of dim 4 stay zero): input x = 4 i + k
-  constexpr int D = KD * KD;
-  const double h = 0.70710678118654752440;
-  // (input k, basis b) -> amplitude; every other entry is an exact zero
-  const double c1r = h * b3r[1], c1i = h * b3i[1];
-#pragma unroll
-  for (int b = 0; b < D; ++b) {
-    const int a1 = b / KD, a2 = b % KD;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      double re = 0.0, im = 0.0;
-      if (k == 0 && b == 0) re = 1.0;                                        // |00>
-      if (k == 1 && a1 == 0 && a2 == 1) { re = b2r[0]; im = b2i[0]; }        // |01> -> c01 |01>
-      if (k == 1 && a1 == 0 && a2 == 2) { re = b2r[1]; im = b2i[1]; }        //        + c0r |0r>
-      if (k == 2 && a1 == 1 && a2 == 0) { re = b2r[0]; im = b2i[0]; }        // |10>: atom-swap mirror
-      if (k == 2 && a1 == 2 && a2 == 0) { re = b2r[1]; im = b2i[1]; }
-      if (k == 3 && a1 == 1 && a2 == 1) { re = b3r[0]; im = b3i[0]; }        // |11> -> c11 |11>
-      if (k == 3 && ((a1 == 1 && a2 == 2) || (a1 == 2 && a2 == 1))) { re = c1r; im = c1i; }   // c+ |+>
-      if (k == 3 && a1 == 2 && a2 == 2) { re = b3r[2]; im = b3i[2]; }        //  + crr |rr>
-      st[(int64_t)(2 * b) * lds + 4 * i + k] = re;
-      st[(int64_t)(2 * b + 1) * lds + 4 * i + k] = im;
-    }
-  }
-  uint32_t stat = valid ? 0u : RYD_STATUS_BAD_INPUT;
-  if (over_cap) stat |= RYD_STATUS_STEP_CAP;
-  bool fin = true;
-#pragma unroll
-  for (int e = 0; e < 2; ++e) fin = fin && isfinite(b2r[e]) && isfinite(b2i[e]);
-#pragma unroll
-  for (int e = 0; e < 3; ++e) fin = fin && isfinite(b3r[e]) && isfinite(b3i[e]);
-  if (!fin) stat |= RYD_STATUS_NONFINITE;
-  // compute_CZ_fidelity pure branch (RG/simulation.py:483-631), as ket_cheb_kernel
-  const double orr[4] = {1.0, b2r[0], b2r[0], b3r[0]}, oii[4] = {0.0, b2i[0], b2i[0], b3i[0]};
-  double p[4], ph[4];
-#pragma unroll
-  for (int x = 0; x < 4; ++x) {
-    p[x] = orr[x] * orr[x] + oii[x] * oii[x];
-    ph[x] = atan2(oii[x], orr[x]);
-  }
-  double cp = ph[3] - ph[1] - ph[2] + ph[0];
-  cp = cp + M_PI;
-  cp = cp - 2.0 * M_PI * floor(cp / (2.0 * M_PI));
-  cp = cp - M_PI;
-  const double err = fmin(fabs(cp - M_PI), fabs(cp + M_PI));
-  const double cerr = cos(err / 2);
-  const double pen = cerr * cerr;
-  const double avgp = 0.25 * (p[0] + p[1] + p[2] + p[3]);
-  const double avgf = 0.25 * (p[0] + p[1] + p[2] + p[3] * pen);
-  double nrm11 = 0.0;
-#pragma unroll
-  for (int e = 0; e < 3; ++e) nrm11 += b3r[e] * b3r[e] + b3i[e] * b3i[e];
-#pragma unroll
-  for (int x = 0; x < 4; ++x) {
-    sm[(int64_t)(RYD_S_POP0 + x) * ldm + i] = p[x];
-    sm[(int64_t)(RYD_S_OV_RE0 + x) * ldm + i] = orr[x];
-    sm[(int64_t)(RYD_S_OV_IM0 + x) * ldm + i] = oii[x];
-  }
-  sm[(int64_t)RYD_S_AVG_POP * ldm + i] = avgp;
-  sm[(int64_t)RYD_S_CTRL_PHASE * ldm + i] = cp;
-  sm[(int64_t)RYD_S_PENALTY * ldm + i] = pen;
-  sm[(int64_t)RYD_S_AVG_F * ldm + i] = avgf;
-  sm[(int64_t)RYD_S_NMV_USEFUL * ldm + i] = (double)nseg_used;     // block segment applications
-  sm[(int64_t)RYD_S_NMV_EXEC * ldm + i] = (double)nseg_used;
-  sm[(int64_t)RYD_S_TRACE11 * ldm + i] = nrm11;
-  sm[(int64_t)RYD_S_NSQUARE * ldm + i] = (double)nbuild;           // propagator builds
-  status[i] = stat;
+  constexpr bool STATE = true;
+#include "ryd_ket_block_body.inc"
+}
+
+// the summary-only twin (launch() with a null state pointer)
+template <int PROTO, int KD>
+__global__ __launch_bounds__(BLOCK) void ket_block_nostate_kernel(
+    const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st, int64_t lds,
+    double* __restrict__ sm, int64_t ldm, uint32_t* __restrict__ status, int n_steps, int shape) {
+  constexpr bool STATE = false;
+#include "ryd_ket_block_body.inc"
 }
 #undef CMUL_RE
 #undef CMUL_IM
@@ -2553,7 +2420,36 @@ KernelFn pick_kernel(const ryd_batch_desc* d) {
   return nullptr;
 }
 
-int validate(const ryd_batch_desc* d, int64_t n, int64_t ldp, int64_t lds, int64_t ldm) {
+// the summary-only twin of the ket_block kernel pick_kernel() returns for d
+KernelFn pick_ket_block_nostate(const ryd_batch_desc* d) {
+  if (d->evolution != RYD_EVOL_KET || !use_ket_block(d)) return nullptr;
+  switch (d->protocol) {
+    case RYD_PROTO_LP_SQUARE:
+      return d->dim == 4 ? ket_block_nostate_kernel<RYD_PROTO_LP_SQUARE, 4> : ket_block_nostate_kernel<RYD_PROTO_LP_SQUARE, 3>;
+    case RYD_PROTO_LP_SHAPED:
+      return d->dim == 4 ? ket_block_nostate_kernel<RYD_PROTO_LP_SHAPED, 4> : ket_block_nostate_kernel<RYD_PROTO_LP_SHAPED, 3>;
+    case RYD_PROTO_BANGBANG:
+      return d->dim == 4 ? ket_block_nostate_kernel<RYD_PROTO_BANGBANG, 4> : ket_block_nostate_kernel<RYD_PROTO_BANGBANG, 3>;
+    case RYD_PROTO_SMOOTH_JP:
+      return d->dim == 4 ? ket_block_nostate_kernel<RYD_PROTO_SMOOTH_JP, 4> : ket_block_nostate_kernel<RYD_PROTO_SMOOTH_JP, 3>;
+  }
+  return nullptr;
+}
+
+// The descriptors launch_kernels<false> has a store-free kernel for: the dim-3 identical-atom
+// Lindblad path of the auto method for constant-|Omega| schedules (sym16) and the ket block
+// kernel.  Every other one (shaped16, the dim-4 propagator, the per-lane Chebyshev kernels,
+// lindblad_prop_kernel and the jp split, ket_cheb_kernel, the squaring method, DOPRI5) runs
+// into a scratch buffer.  shaped16 and lindblad4_prop_kernel had twins whose median did not lie
+// below the storing kernel's range in every round (4.8 ms and 0.12 ms of arithmetic per C2
+// launch against the 8 and 11.5 MB of stores; profiles/summary_only/), so they were not kept.
+bool has_nostate_kernel(const ryd_batch_desc* d) {
+  if (d->method == RYD_METHOD_DOPRI5) return false;
+  return use_sym16(d) || pick_ket_block_nostate(d) != nullptr;
+}
+
+// has_state = false: a summary-only call (null state pointer), whose ld_state is ignored
+int validate(const ryd_batch_desc* d, int64_t n, int64_t ldp, int64_t lds, int64_t ldm, bool has_state = true) {
   if (!d) return fail(RYD_ERR_INVALID, "desc is NULL");
   if (d->abi_version != RYD_ABI_VERSION) return fail(RYD_ERR_INVALID, "abi_version mismatch");
   if (d->dim != 3 && d->dim != 4) return fail(RYD_ERR_UNSUPPORTED, "hilbert_space_dim must be 3 or 4");
@@ -2579,7 +2475,7 @@ int validate(const ryd_batch_desc* d, int64_t n, int64_t ldp, int64_t lds, int64
   if (d->protocol == RYD_PROTO_BANGBANG && (d->n_steps < 1 || d->n_steps > 8))
     return fail(RYD_ERR_INVALID, "BANGBANG needs 1 <= n_steps (max segments) <= 8");
   if (n < 0) return fail(RYD_ERR_INVALID, "n < 0");
-  if (ldp < n || lds < 4 * n || ldm < n) return fail(RYD_ERR_INVALID, "leading dimension too small");
+  if (ldp < n || (has_state && lds < 4 * n) || ldm < n) return fail(RYD_ERR_INVALID, "leading dimension too small");
   return RYD_OK;
 }
 
@@ -2641,9 +2537,12 @@ int launch_jp_split(const ryd_batch_desc* d, const double* dp, int64_t n, int64_
   return RYD_OK;
 }
 
-int launch(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, double* ds, int64_t lds,
-           double* dm, int64_t ldm, uint32_t* dstat, hipStream_t stream) {
-  if (n == 0) return RYD_OK;
+// The kernel launch of one batch.  STATE = false (launch() alone passes it, with ds = NULL, and
+// only for a descriptor that has_nostate_kernel()) takes the summary-only twin of the kernel
+// the descriptor selects, with the same grid and arguments.
+template <bool STATE>
+int launch_kernels(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, double* ds, int64_t lds,
+                   double* dm, int64_t ldm, uint32_t* dstat, hipStream_t stream) {
   if (d->method == RYD_METHOD_DOPRI5) {
     using DFn = void (*)(const double*, int64_t, int64_t, double*, int64_t, double*, int64_t,
                          uint32_t*, int, int, double, double, int64_t);
@@ -2694,6 +2593,10 @@ int launch(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, do
     SFn f = d->protocol == RYD_PROTO_LP_SQUARE ? lindblad_sym16_kernel<RYD_PROTO_LP_SQUARE>
             : d->protocol == RYD_PROTO_SMOOTH_JP ? lindblad_sym16_kernel<RYD_PROTO_SMOOTH_JP>
                                                   : lindblad_sym16_kernel<RYD_PROTO_BANGBANG>;
+    if constexpr (!STATE)
+      f = d->protocol == RYD_PROTO_LP_SQUARE ? lindblad_sym16_nostate_kernel<RYD_PROTO_LP_SQUARE>
+          : d->protocol == RYD_PROTO_SMOOTH_JP ? lindblad_sym16_nostate_kernel<RYD_PROTO_SMOOTH_JP>
+                                                : lindblad_sym16_nostate_kernel<RYD_PROTO_BANGBANG>;
     const int64_t blocks = (n + S16_PPW - 1) / S16_PPW;
     if (blocks > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
     int ns = d->n_steps, sh = d->shape;
@@ -2730,6 +2633,9 @@ int launch(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, do
         static_assert(RYD_P_XI_IM == 14, "the largest LP-square parameter column");
         const bool p32 = sym16_param32_enabled() && ldp <= (0x7fffffffLL / 8 - n) / 14;
         BFn fb = p32 ? lindblad_sym16_kernel<RYD_PROTO_LP_SQUARE, 2> : lindblad_sym16_kernel<RYD_PROTO_LP_SQUARE, 1>;
+        if constexpr (!STATE)
+          fb = p32 ? lindblad_sym16_nostate_kernel<RYD_PROTO_LP_SQUARE, 2>
+                   : lindblad_sym16_nostate_kernel<RYD_PROTO_LP_SQUARE, 1>;
         int gpc = pl.gpc, noh = eh && eh[0] == '1';
         int wt = wtm >= 0 ? wtm : S16_WT_AUTO;
         void* bargs[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&ds, (void*)&lds, (void*)&dm, (void*)&ldm,
@@ -2748,7 +2654,7 @@ int launch(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, do
   }
   if (use_propagator(d) && d->protocol == RYD_PROTO_SMOOTH_JP && jp_split_enabled())
     return launch_jp_split(d, dp, n, ldp, ds, lds, dm, ldm, dstat, stream);
-  KernelFn k = pick_kernel(d);
+  KernelFn k = STATE ? pick_kernel(d) : pick_ket_block_nostate(d);
   if (!k) return fail(RYD_ERR_UNSUPPORTED, "no kernel for this descriptor");
   const int64_t blocks = use_propagator(d) ? (n + PPB - 1) / PPB
                         : use_ket_block(d) ? (n + BLOCK - 1) / BLOCK : (4 * n + BLOCK - 1) / BLOCK;
@@ -2757,6 +2663,38 @@ int launch(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, do
   void* args[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&ds, (void*)&lds, (void*)&dm,
                   (void*)&ldm, (void*)&dstat, (void*)&ns, (void*)&sh};
   HIPCHK(hipLaunchKernel((const void*)k, dim3((unsigned)blocks), dim3(BLOCK), args, 0, stream));
+  return RYD_OK;
+}
+
+// RYD_NOSTATE=0 sends every summary-only launch down the scratch-buffer path, the storing
+// kernels (A/B measurements and the cross-check of the store-free twins); read per launch
+bool nostate_enabled() {
+  const char* e = getenv("RYD_NOSTATE");
+  return !(e && e[0] == '0');
+}
+
+// One batch on `stream`.  ds = NULL is a summary-only call, and this is the one place that
+// knows: the descriptor's store-free twin where it has one, otherwise the ordinary kernel into
+// a scratch state buffer from the private stream-ordered pool, freed on the stream (nothing
+// copies it; as launch_jp_split's workspace).  No kernel that stores state sees a null pointer.
+int launch(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, double* ds, int64_t lds,
+           double* dm, int64_t ldm, uint32_t* dstat, hipStream_t stream) {
+  if (n == 0) return RYD_OK;
+  if (ds) return launch_kernels<true>(d, dp, n, ldp, ds, lds, dm, ldm, dstat, stream);
+  if (nostate_enabled() && has_nostate_kernel(d))
+    return launch_kernels<false>(d, dp, n, ldp, nullptr, 0, dm, ldm, dstat, stream);
+  const int sw = ryd_state_width(d->evolution, d->dim);
+  if (sw <= 0) return fail(RYD_ERR_INVALID, "bad evolution");
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  hipMemPool_t pool = jp_pool(dev);
+  if (!pool) return fail(RYD_ERR_ALLOC, "scratch state pool creation failed");
+  double* W = nullptr;
+  HIPCHK(hipMallocFromPoolAsync((void**)&W, sizeof(double) * (size_t)sw * 4 * (size_t)n, pool, stream));
+  const int rc = launch_kernels<true>(d, dp, n, ldp, W, 4 * n, dm, ldm, dstat, stream);
+  hipError_t ef = hipFreeAsync(W, stream);           // on the error path too
+  if (rc) return rc;
+  if (ef != hipSuccess) return fail(RYD_ERR_HIP, std::string("scratch state free: ") + hipGetErrorString(ef));
   return RYD_OK;
 }
 
@@ -3361,7 +3299,7 @@ int ryd_run_batch_device(ryd_handle* h, int slot, const ryd_batch_desc* desc, co
                          double* d_summary, int64_t ld_summary, uint32_t* d_status, void* stream,
                          float* elapsed_ms) {
   if (!h || slot < 0 || slot >= (int)h->dev.size()) return fail(RYD_ERR_INVALID, "bad handle/slot");
-  int rc = validate(desc, n, ld_params, ld_state, ld_summary);
+  int rc = validate(desc, n, ld_params, ld_state, ld_summary, d_state != nullptr);
   if (rc) return rc;
   HIPCHK(hipSetDevice(h->dev[slot]));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream[slot];
@@ -3379,17 +3317,23 @@ int ryd_run_batch(ryd_handle* h, const ryd_batch_desc* desc, const double* param
                   int64_t ld_params, double* out_state, int64_t ld_state, double* out_summary,
                   int64_t ld_summary, uint32_t* out_status, ryd_stats* stats) {
   if (!h) return fail(RYD_ERR_INVALID, "handle is NULL");
-  int rc = validate(desc, n, ld_params, ld_state, ld_summary);
+  int rc = validate(desc, n, ld_params, ld_state, ld_summary, out_state != nullptr);
   if (rc) return rc;
-  if (n > 0 && (!params || !out_state || !out_summary || !out_status))
+  if (n > 0 && (!params || !out_summary || !out_status))
     return fail(RYD_ERR_INVALID, "NULL buffer");
   const int sw = ryd_state_width(desc->evolution, desc->dim);
-  const std::vector<HostOut> outs = {{out_state, ld_state, sw, 4}, {out_summary, ld_summary, RYD_NSUMMARY, 1}};
+  // summary-only (out_state NULL): the summary is the only output array, so the device
+  // workspace, the staging buffer, the D2H and the unpack carry no state rows
+  std::vector<HostOut> outs;
+  if (out_state) outs.push_back({out_state, ld_state, sw, 4});
+  outs.push_back({out_summary, ld_summary, RYD_NSUMMARY, 1});
   double kms, hms, dms;
   rc = run_partitioned(
       h, params, n, ld_params, outs, out_status,
       [&](const double* dp, int64_t cnt, int64_t ldp, int64_t, const std::vector<double*>& o, uint32_t* dst,
-          hipStream_t s) { return launch(desc, dp, cnt, ldp, o[0], 4 * cnt, o[1], cnt, dst, s); },
+          hipStream_t s) {
+        return launch(desc, dp, cnt, ldp, out_state ? o[0] : nullptr, 4 * cnt, o.back(), cnt, dst, s);
+      },
       kms, hms, dms);
   if (rc) return rc;
   if (stats) {

@@ -961,6 +961,8 @@ __device__ __forceinline__ void seg_apply(const double (&u)[NS], const SegRow01&
   z = acc1;
 }
 
+// STATE = false: the summary-only twin (lindblad_sym16_nostate_kernel) -- no state rows staged or stored
+template <bool STATE = true>
 __device__ __forceinline__ void sym16_epilogue(double t, double z, double s00, double cp, double sp,
                                                const SegRot& rw, bool valid, bool over_cap, int nuse, int nexec,
                                                int nsq, int l, int p, int64_t blk, int64_t n,
@@ -1051,6 +1053,21 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
   (void)shape;
   constexpr int BAL = PROTO < 0 ? 1 : 0;     // 0, and dependent: the balanced form's statements are discarded
   constexpr int gpc = 0, nohandoff = 0, wt = 0, p32 = 0;
+  constexpr bool STATE = true;
+#include "ryd_sym16_body.inc"
+}
+
+// The summary-only twin (launch() with a null state pointer): the same body, the epilogue
+// without the state rows.  `st` is NULL and `lds` unread.
+template <int PROTO>
+__global__ __launch_bounds__(S16_BLOCK) __attribute__((amdgpu_waves_per_eu(PROTO == RYD_PROTO_BANGBANG ? 3 : RYD_S16_WAVES, 8))) void
+lindblad_sym16_nostate_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st,
+                              int64_t lds, double* __restrict__ sm, int64_t ldm, uint32_t* __restrict__ status,
+                              int n_steps, int shape, int st32) {
+  (void)shape;
+  constexpr int BAL = PROTO < 0 ? 1 : 0;
+  constexpr int gpc = 0, nohandoff = 0, wt = 0, p32 = 0;
+  constexpr bool STATE = false;
 #include "ryd_sym16_body.inc"
 }
 
@@ -1068,6 +1085,19 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
                       int n_steps, int gpc, int st32, int nohandoff, int wt) {
   static_assert(PROTO == RYD_PROTO_LP_SQUARE && (BAL == 1 || BAL == 2), "the balanced form is built for LP square");
   constexpr int p32 = BAL == 2;
+  constexpr bool STATE = true;
+#include "ryd_sym16_body.inc"
+}
+
+// the balanced form's summary-only twin (`wt & S16_WT_SUMMARY` still selects write-through)
+template <int PROTO, int BAL>
+__global__ __launch_bounds__(S16_BLOCK * S16_BAL_MAXW) __attribute__((amdgpu_waves_per_eu(RYD_S16_WAVES, 8))) void
+lindblad_sym16_nostate_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st,
+                              int64_t lds, double* __restrict__ sm, int64_t ldm, uint32_t* __restrict__ status,
+                              int n_steps, int gpc, int st32, int nohandoff, int wt) {
+  static_assert(PROTO == RYD_PROTO_LP_SQUARE && (BAL == 1 || BAL == 2), "the balanced form is built for LP square");
+  constexpr int p32 = BAL == 2;
+  constexpr bool STATE = false;
 #include "ryd_sym16_body.inc"
 }
 
@@ -1145,6 +1175,7 @@ __device__ __forceinline__ void s16_store_summary(double v, double c, uint32_t s
   }
 }
 
+template <bool STATE>
 __device__ __forceinline__ void sym16_epilogue(double t, double z, double s00, double cp, double sp,
                                                const SegRot& rw, bool valid, bool over_cap, int nuse, int nexec,
                                                int nsq, int l, int p, int64_t blk, int64_t n,
@@ -1164,40 +1195,42 @@ __device__ __forceinline__ void sym16_epilogue(double t, double z, double s00, d
     if (r == SEG_P) t = 0.5 * (pv - mv);
   }
   // ---- stage the 4 x 25 sector rows of each point (in Ut) and store them coalesced
-  double (*Ro)[4][NC] = reinterpret_cast<double (*)[4][NC]>(&Ut[0][0][0]);
-  wave_sync();                               // the last transpose is read
-#pragma unroll
-  for (int e = r; e < 4 * NC; e += 16) (&Ro[p][0][0])[e] = 0.0;
-  wave_sync();
-  if (lane_ok) {
-    // lane -> (ia, ja) in segment order (after the conversion above lanes 10, 11, 14 hold
-    // (3,3), (3,4), (4,4)): nibble tables
-    const int ia = (int)((0x0421332211100000ull >> (4 * r)) & 15);
-    const int ja = (int)((0x0422434343124310ull >> (4 * r)) & 15);
-    Ro[p][3][5 * ia + ja] = t;
-    Ro[p][3][5 * ja + ia] = t;
-  }
-  if (r < 5) {
-    const int mz = (int)((0x24310u >> (4 * r)) & 15);  // z lanes 0-4 hold (0,0) (0,1) (0,3) (0,4) (0,2)
-    Ro[p][1][mz] = z;
-    Ro[p][2][5 * mz] = z;
-  }
-  if (r == 0) Ro[p][0][0] = s00;
-  wave_sync();
-  // lane l stores column cc = l % 16 (point cc / 4, input cc % 4) of rows l / 16 + 4 j
+  // (STATE = false, the summary-only twin: nothing is staged or stored; the summary below is
+  // formed from registers either way)
   const int64_t i0 = blk * S16_PPW;
-  {
-    const int cc = l & 15, pp = cc >> 2, k = cc & 3;
-    const bool in = i0 + pp < n;
-    double v[7];
+  if constexpr (STATE) {
+    double (*Ro)[4][NC] = reinterpret_cast<double (*)[4][NC]>(&Ut[0][0][0]);
+    wave_sync();                               // the last transpose is read
 #pragma unroll
-    for (int j = 0; j < 7; ++j)              // rows 25 .. 27 (j = 6, lanes >= 16): read inside Ut, never stored
-      v[j] = (&Ro[pp][k][0])[(l >> 4) + 4 * j];
-    static_assert(NC == 25, "rows l/16 + 4 j: j < 6 always inside, j = 6 on the first 16 lanes only");
-#ifndef RYD_S16_PROBE_NOSTATE                // timing-only probe build: no state stores, wrong results
-    if (wt & S16_WT_STATE) s16_store_state<true>(v, st, lds, i0, l, cc, in, st32);
-    else s16_store_state<false>(v, st, lds, i0, l, cc, in, st32);
-#endif
+    for (int e = r; e < 4 * NC; e += 16) (&Ro[p][0][0])[e] = 0.0;
+    wave_sync();
+    if (lane_ok) {
+      // lane -> (ia, ja) in segment order (after the conversion above lanes 10, 11, 14 hold
+      // (3,3), (3,4), (4,4)): nibble tables
+      const int ia = (int)((0x0421332211100000ull >> (4 * r)) & 15);
+      const int ja = (int)((0x0422434343124310ull >> (4 * r)) & 15);
+      Ro[p][3][5 * ia + ja] = t;
+      Ro[p][3][5 * ja + ia] = t;
+    }
+    if (r < 5) {
+      const int mz = (int)((0x24310u >> (4 * r)) & 15);  // z lanes 0-4 hold (0,0) (0,1) (0,3) (0,4) (0,2)
+      Ro[p][1][mz] = z;
+      Ro[p][2][5 * mz] = z;
+    }
+    if (r == 0) Ro[p][0][0] = s00;
+    wave_sync();
+    // lane l stores column cc = l % 16 (point cc / 4, input cc % 4) of rows l / 16 + 4 j
+    {
+      const int cc = l & 15, pp = cc >> 2, k = cc & 3;
+      const bool in = i0 + pp < n;
+      double v[7];
+#pragma unroll
+      for (int j = 0; j < 7; ++j)              // rows 25 .. 27 (j = 6, lanes >= 16): read inside Ut, never stored
+        v[j] = (&Ro[pp][k][0])[(l >> 4) + 4 * j];
+      static_assert(NC == 25, "rows l/16 + 4 j: j < 6 always inside, j = 6 on the first 16 lanes only");
+      if (wt & S16_WT_STATE) s16_store_state<true>(v, st, lds, i0, l, cc, in, st32);
+      else s16_store_state<false>(v, st, lds, i0, l, cc, in, st32);
+    }
   }
 #ifdef RYD_S16_PROF
   S16_MARK(7);

@@ -1,7 +1,7 @@
 // ryd_sym16_body.inc -- the body of lindblad_sym16_kernel, included by ryd_sym16.inc inside
 // each of its two kernel templates (textually, so that the one-wave kernels compile exactly
 // as they did when this was their own body).  The including function provides PROTO, the
-// kernel parameters, and
+// kernel parameters, STATE (false: the summary-only twins, whose epilogue stores no state rows) and
 //   BAL = 0: one wave per workgroup, one job (the three one-wave kernels);
 //   BAL = 1: a wave of the balanced form's workgroup (LP square; `gpc` groups per workgroup,
 //            `nohandoff`, `wt`): every LDS array gets a copy per wave, the job comes from the role
@@ -355,6 +355,6 @@
       }
     }
 #endif
-    return sym16_epilogue(t, z, s00, cp, sp, rw_out, valid, over_cap, nuse, nexec, nsq, lid, pl, b2, n, st, lds, sm,
-                          ldm, status, st32 != 0, wt, Ut S16_PROF_PASS);
+    return sym16_epilogue<STATE>(t, z, s00, cp, sp, rw_out, valid, over_cap, nuse, nexec, nsq, lid, pl, b2, n, st, lds, sm,
+                                 ldm, status, st32 != 0, wt, Ut S16_PROF_PASS);
   }

@@ -90,7 +90,7 @@ def mixed_phase(state: np.ndarray, n: int, dim: int = 3, gauge_check: bool = Tru
 class EngineResult:
     evolution: str
     n: int
-    state: np.ndarray       # (width, 4n)
+    state: Optional[np.ndarray]   # (width, 4n); None after a summary-only run (states=False)
     summary: np.ndarray     # (NSUMMARY, n)
     status: np.ndarray      # (n,) uint32
     kernel_ms: float
@@ -106,12 +106,18 @@ class EngineResult:
     def populations(self) -> np.ndarray:
         return self.summary[N.S["POP0"]:N.S["POP0"] + 4].T
 
+    def _need_state(self, what: str) -> None:
+        if self.state is None:
+            raise ValueError(f"{what}: the run was summary-only (states=False), no state rows were kept")
+
     def rho(self) -> np.ndarray:
         assert self.evolution == "lindblad"
+        self._need_state("rho()")
         return expand_rho(self.state, self.n, self.dim)
 
     def kets(self) -> np.ndarray:
         assert self.evolution == "ket"
+        self._need_state("kets()")
         return expand_ket(self.state, self.n, self.dim)
 
 
@@ -278,7 +284,11 @@ class Engine:
 
     def run(self, params: np.ndarray, protocol: str, evolution: str, n_steps: Optional[int] = None,
             shape: str = "square", method: str = "chebyshev", rtol: float = 1e-10,
-            atol: float = 1e-12, max_steps: int = 10 ** 7, dim: int = 3) -> EngineResult:
+            atol: float = 1e-12, max_steps: int = 10 ** 7, dim: int = 3,
+            states: bool = True) -> EngineResult:
+        """``states=False`` is a summary-only run: no state array is allocated, the library
+        gets a NULL state pointer (no state rows cross the bus) and ``EngineResult.state`` is
+        None; summary and status are those of the full run bit for bit."""
         params = np.ascontiguousarray(params, dtype=np.float64)
         if params.shape[0] != N.NPARAM:
             raise ValueError(f"params must have shape ({N.NPARAM}, n)")
@@ -291,13 +301,14 @@ class Engine:
         # every kernel writes every state row and summary column of every point, so the
         # outputs need no zero fill (np.zeros of the 8 MB C2 state costs ~0.3 ms of page
         # zeroing per call; tools/unpack_probe.py)
-        state = np.empty((w, 4 * n), dtype=np.float64)
+        state = np.empty((w, 4 * n), dtype=np.float64) if states else None
         summ = np.empty((N.NSUMMARY, n), dtype=np.float64)
         status = np.zeros(n, dtype=np.uint32)
         st = N.Stats()
         dptr = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         N.check(self.lib.ryd_run_batch(
-            self.handle, ctypes.byref(desc), dptr(params), n, n, dptr(state), 4 * n, dptr(summ), n,
+            self.handle, ctypes.byref(desc), dptr(params), n, n, dptr(state) if states else None, 4 * n,
+            dptr(summ), n,
             status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(st)))
         return EngineResult(evolution, n, state, summ, status, st.kernel_ms, st.h2d_ms, st.d2h_ms,
                             st.matvec_useful, st.matvec_exec, dim)
@@ -390,8 +401,9 @@ class DeviceBatch:
 
     def __init__(self, engine: Engine, params: np.ndarray, protocol: str, evolution: str,
                  n_steps: Optional[int] = None, shape: str = "square", slot: int = 0,
-                 method: str = "chebyshev", dim: int = 3):
+                 method: str = "chebyshev", dim: int = 3, states: bool = True):
         self.eng, self.slot = engine, slot
+        self.states = states                 # False: summary-only, no d_state (NULL is passed)
         lib = engine.lib
         params = np.ascontiguousarray(params, dtype=np.float64)
         self.n = n = params.shape[1]
@@ -409,7 +421,7 @@ class DeviceBatch:
             self._bufs.append(p)
             return p
         self.d_params = alloc(params.nbytes)
-        self.d_state = alloc(8 * self.width * 4 * n)
+        self.d_state = alloc(8 * self.width * 4 * n) if states else None
         self.d_summary = alloc(8 * N.NSUMMARY * n)
         self.d_status = alloc(4 * n)
         N.check(lib.ryd_memcpy_h2d(engine.handle, slot, self.d_params, params.ctypes.data, params.nbytes))
@@ -439,10 +451,11 @@ class DeviceBatch:
 
     def fetch(self) -> EngineResult:
         lib, h, s = self.eng.lib, self.eng.handle, self.slot
-        state = np.zeros((self.width, 4 * self.n))
+        state = np.zeros((self.width, 4 * self.n)) if self.states else None
         summ = np.zeros((N.NSUMMARY, self.n))
         status = np.zeros(self.n, dtype=np.uint32)
-        N.check(lib.ryd_memcpy_d2h(h, s, state.ctypes.data, self.d_state, state.nbytes))
+        if self.states:
+            N.check(lib.ryd_memcpy_d2h(h, s, state.ctypes.data, self.d_state, state.nbytes))
         N.check(lib.ryd_memcpy_d2h(h, s, summ.ctypes.data, self.d_summary, summ.nbytes))
         N.check(lib.ryd_memcpy_d2h(h, s, status.ctypes.data, self.d_status, status.nbytes))
         return EngineResult(self.evolution, self.n, state, summ, status, 0.0, 0.0, 0.0,
@@ -462,8 +475,9 @@ class DeviceSweep:
     engine on the slot's stream."""
 
     def __init__(self, engine: Engine, inp, evolution: str = "lindblad", slot: int = 0,
-                 n_steps: Optional[int] = None, method: str = "chebyshev"):
+                 n_steps: Optional[int] = None, method: str = "chebyshev", states: bool = True):
         self.eng, self.slot, self.inp = engine, slot, inp
+        self.states = states                 # False: summary-only, no d_state (NULL is passed)
         lib = engine.lib
         self.n = n = inp.n
         self.dim = inp.dim
@@ -486,7 +500,7 @@ class DeviceSweep:
         self.d_in = alloc(8 * self.k * n)
         self.d_params = alloc(8 * N.NPARAM * n)
         self.d_warn = alloc(4 * n)
-        self.d_state = alloc(8 * self.width * 4 * n)
+        self.d_state = alloc(8 * self.width * 4 * n) if states else None
         self.d_summary = alloc(8 * N.NSUMMARY * n)
         self.d_status = alloc(4 * n)
         self.upload()
@@ -537,10 +551,11 @@ class DeviceSweep:
 
     def fetch(self) -> EngineResult:
         lib, h, s = self.eng.lib, self.eng.handle, self.slot
-        state = np.zeros((self.width, 4 * self.n))
+        state = np.zeros((self.width, 4 * self.n)) if self.states else None
         summ = np.zeros((N.NSUMMARY, self.n))
         status = np.zeros(self.n, dtype=np.uint32)
-        N.check(lib.ryd_memcpy_d2h(h, s, state.ctypes.data, self.d_state, state.nbytes))
+        if self.states:
+            N.check(lib.ryd_memcpy_d2h(h, s, state.ctypes.data, self.d_state, state.nbytes))
         N.check(lib.ryd_memcpy_d2h(h, s, summ.ctypes.data, self.d_summary, summ.nbytes))
         N.check(lib.ryd_memcpy_d2h(h, s, status.ctypes.data, self.d_status, status.nbytes))
         _, warn = self.fetch_params()

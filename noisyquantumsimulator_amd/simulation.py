@@ -427,6 +427,16 @@ PIPELINE_CHUNKS = 4
 PIPELINE_MIN_CHUNK = 2048
 
 
+def needs_state(evolution: str, phase_penalty: str, return_states: bool, process_fidelity: bool) -> bool:
+    """Whether an engine pass of ``simulate_CZ_gate_batch`` must bring the state rows back.
+    The caller asked for them (``return_states``), the gauge-invariant ``process_fidelity``
+    is built from them, or the points are Lindblad points under ``phase_penalty="reference"``,
+    whose LAPACK epilogue reads rho.  Everything else -- noise-free (ket) points, whose
+    metrics are all summary columns, and ``phase_penalty="none"`` sweeps -- runs
+    summary-only (``Engine.run(states=False)``)."""
+    return bool(return_states or process_fidelity or (evolution == "lindblad" and phase_penalty == "reference"))
+
+
 def simulate_CZ_gate_batch(simulation_inputs, n: Optional[int] = None, *, species="Rb87",
                            n_rydberg=70, qubit_0=(1, 0), qubit_1=(2, 0), hilbert_space_dim: int = 3,
                            tweezer_power=30e-3, tweezer_waist=1.0e-6, tweezer_wavelength_nm=None,
@@ -516,7 +526,8 @@ def simulate_CZ_gate_batch(simulation_inputs, n: Optional[int] = None, *, specie
                 idx = lo + loc
                 t0 = time.perf_counter()
                 prm = E.pack_params(b, loc)
-                r = eng.run(prm, key, evol, shape=shape, method=method if dim == 3 else "chebyshev", dim=dim)
+                r = eng.run(prm, key, evol, shape=shape, method=method if dim == 3 else "chebyshev", dim=dim,
+                            states=needs_state(evol, phase_penalty, return_states, process_fidelity))
                 coh = None
                 if process_fidelity and evol == "lindblad":
                     coh, cst = eng.run_coherences(prm, key, shape=shape, dim=dim)
