@@ -306,6 +306,25 @@ int         ryd_lp_unsquared(void);
  * every consumer compute the producer's part itself (read per launch). */
 int64_t     ryd_sym16_balance_plan(int64_t n, int cus, int gpc_override, int64_t* head, int32_t* role,
                                    int64_t* job, uint8_t* present, int64_t cap);
+/* The kernel family ryd_run_batch / ryd_run_batch_device launch for `desc` (pure host code, no
+ * handle or device needed): a RYD_PATH_* value, from the same selection function the launch
+ * calls, under the environment switches as they stand at the call (they are read per launch).
+ * has_state = 0 asks about a summary-only call (NULL state pointer): RYD_PATH_NOSTATE is
+ * OR-ed in exactly when that call runs the path's store-free twin and not the storing kernel
+ * into a scratch buffer.  A descriptor the batch calls reject returns their negative
+ * RYD_ERR_* (ryd_last_error is set).  The identical-atom kernel's one-wave or balanced launch
+ * form is not part of the answer: ryd_sym16_balance_plan reports it. */
+#define RYD_PATH_DOPRI5        1   /* lindblad_dopri5_kernel                                */
+#define RYD_PATH_DIM4_PROP     2   /* lindblad4_prop_kernel */
+#define RYD_PATH_SHAPED16      3   /* lindblad_shaped16_kernel */
+#define RYD_PATH_SYM16         4   /* lindblad_sym16_kernel */
+#define RYD_PATH_JP_SPLIT      5   /* jp_rows_kernel -> jp_frame_kernel */
+#define RYD_PATH_LINDBLAD_PROP 6   /* lindblad_prop_kernel                                   */
+#define RYD_PATH_LINDBLAD_CHEB 7   /* lindblad_cheb_kernel / lindblad4_cheb_kernel           */
+#define RYD_PATH_KET_BLOCK     8   /* ket_block_kernel */
+#define RYD_PATH_KET_CHEB      9   /* ket_cheb_kernel                                        */
+#define RYD_PATH_NOSTATE       256 /* flag: the store-free twin (SYM16 and KET_BLOCK have one) */
+int         ryd_batch_path(const ryd_batch_desc* desc, int has_state);
 int         ryd_device_count(int* count);
 
 int ryd_create(const int* device_ids, int n_devices, ryd_handle** out);

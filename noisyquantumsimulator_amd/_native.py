@@ -23,6 +23,9 @@ EVOL = {"lindblad": 0, "ket": 1}
 METHOD = {"chebyshev": 0, "dopri5": 1, "cheb_vector": 2, "cheb_squaring": 3}
 SHAPE = {"square": 0, "gaussian": 1, "cosine": 2, "blackman": 3}
 FLAG_SYMMETRIC_ATOMS = 1
+# ryd_batch_path: the kernel family of a batch descriptor; NOSTATE is a flag OR-ed in
+PATH = dict(DOPRI5=1, DIM4_PROP=2, SHAPED16=3, SYM16=4, JP_SPLIT=5, LINDBLAD_PROP=6, LINDBLAD_CHEB=7,
+            KET_BLOCK=8, KET_CHEB=9, NOSTATE=256)
 
 P = dict(OMEGA=0, DELTA=1, V=2, DELTA1=3, G1_A=4, G0_A=5, GPHI_A=6, GSC_A=7, G1_B=8, G0_B=9,
          GPHI_B=10, GSC_B=11, TAU=12, XI_RE=13, XI_IM=14, AREA_CORR=15, A=16, OMEGA_MOD=17,
@@ -59,7 +62,7 @@ T_FLAG = {"auto": 0, "rows": 1, "lanes": 2}
 TL_HEAD, TL_SLOT = 4, 8
 
 EXPORTED = ("ryd_abi_version", "ryd_last_error", "ryd_param_count", "ryd_summary_width", "ryd_lp_unsquared",
-            "ryd_sym16_balance_plan",
+            "ryd_sym16_balance_plan", "ryd_batch_path",
             "ryd_state_width", "ryd_device_count", "ryd_create", "ryd_destroy", "ryd_run_batch",
             "ryd_run_batch_device", "ryd_run_coherences", "ryd_run_coherences_device",
             "ryd_run_trajectories", "ryd_run_trajectories_device",
@@ -153,6 +156,7 @@ def load() -> ctypes.CDLL:
         lib.ryd_sym16_balance_plan.argtypes = [i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(i64),
                                                ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(i64),
                                                ctypes.POINTER(ctypes.c_uint8), i64]
+        lib.ryd_batch_path.argtypes = [ctypes.POINTER(BatchDesc), ctypes.c_int]
         lib.ryd_state_width.argtypes = [ctypes.c_int, ctypes.c_int]
         lib.ryd_device_count.argtypes = [ctypes.POINTER(ctypes.c_int)]
         lib.ryd_create.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(vp)]

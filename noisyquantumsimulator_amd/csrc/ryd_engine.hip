@@ -40,6 +40,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -2230,30 +2231,80 @@ int fail(int code, const std::string& msg) {
 using KernelFn = void (*)(const double*, int64_t, int64_t, double*, int64_t, double*, int64_t,
                           uint32_t*, int, int);
 
-// Lindblad runs on the propagator kernel when asked for explicitly, or under the
-// auto method for the protocols whose gate is a product of few propagators: LP
-// square and bang-bang (few long segments), smooth JP (one propagator in the
-// phase frame).  LP shaped (amplitude changes every segment) stays on the
-// state-vector Chebyshev kernel.
-bool use_propagator(const ryd_batch_desc* d) {
-  const bool auto_prop = d->protocol == RYD_PROTO_LP_SQUARE || d->protocol == RYD_PROTO_BANGBANG ||
-                         d->protocol == RYD_PROTO_SMOOTH_JP;
-  return d->dim == 3 && d->evolution == RYD_EVOL_LINDBLAD &&
-         (d->method == RYD_METHOD_CHEB_SQUARING || (d->method == RYD_METHOD_CHEBYSHEV && auto_prop));
+// an off switch of the environment: the variable is set and starts with '0'.  Every switch
+// is read at the launch it governs, never cached: tests alternate them within one process.
+bool is_off(const char* e) { return e && e[0] == '0'; }
+
+// d->protocol (validated) as a compile-time constant: f(std::integral_constant<int, PROTO>)
+template <typename F>
+int with_protocol(int protocol, F&& f) {
+  switch (protocol) {
+    case RYD_PROTO_LP_SQUARE: return f(std::integral_constant<int, RYD_PROTO_LP_SQUARE>{});
+    case RYD_PROTO_LP_SHAPED: return f(std::integral_constant<int, RYD_PROTO_LP_SHAPED>{});
+    case RYD_PROTO_BANGBANG: return f(std::integral_constant<int, RYD_PROTO_BANGBANG>{});
+    default: return f(std::integral_constant<int, RYD_PROTO_SMOOTH_JP>{});
+  }
 }
 
-// Identical atoms under the auto method (LP square, bang-bang, smooth JP): the
-// 16-lane DPP-row kernel of ryd_sym16.inc.  RYD_SYM16=0 falls back to
-// lindblad_prop_kernel / the smooth-JP split pair (A/B measurements, tests); the
-// explicit RYD_METHOD_CHEB_SQUARING always runs those.
-bool use_sym16(const ryd_batch_desc* d) {
-  const char* e = getenv("RYD_SYM16");
-  if (e && e[0] == '0') return false;
-  return d->dim == 3 && d->evolution == RYD_EVOL_LINDBLAD && d->method == RYD_METHOD_CHEBYSHEV &&
-         (d->flags & RYD_FLAG_SYMMETRIC_ATOMS) != 0 &&
-         (d->protocol == RYD_PROTO_LP_SQUARE || d->protocol == RYD_PROTO_BANGBANG ||
-          d->protocol == RYD_PROTO_SMOOTH_JP);
+// One kernel launch, checked against the kernel's own signature: each argument is converted to
+// the parameter it fills (no narrowing, and no change of width: an int is not quietly widened
+// into an int64_t slot), so a wrong count, order or type does not compile.
+template <typename... P, typename... A>
+int launch_typed(void (*kernel)(P...), int64_t blocks, unsigned block, size_t lds_bytes, hipStream_t stream,
+                 A... a) {
+  static_assert(((sizeof(A) == sizeof(P)) && ...), "an argument's width differs from the kernel parameter's");
+  if (blocks > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
+  return [&](P... p) {
+    void* args[] = {(void*)&p...};
+    HIPCHK(hipLaunchKernel((const void*)kernel, dim3((unsigned)blocks), dim3(block), args, lds_bytes, stream));
+    return RYD_OK;
+  }(P{a}...);
 }
+
+// The kernel family a batch descriptor runs (RYD_PATH_*; ryd_batch_path reports it).
+enum BatchPath {
+  PATH_DOPRI5 = RYD_PATH_DOPRI5, PATH_DIM4_PROP = RYD_PATH_DIM4_PROP, PATH_SHAPED16 = RYD_PATH_SHAPED16,
+  PATH_SYM16 = RYD_PATH_SYM16, PATH_JP_SPLIT = RYD_PATH_JP_SPLIT, PATH_LINDBLAD_PROP = RYD_PATH_LINDBLAD_PROP,
+  PATH_LINDBLAD_CHEB = RYD_PATH_LINDBLAD_CHEB, PATH_KET_BLOCK = RYD_PATH_KET_BLOCK, PATH_KET_CHEB = RYD_PATH_KET_CHEB
+};
+
+// The one place that selects a kernel family for a validated descriptor; the first match wins
+// ("Selection order").  Each =0 switch keeps the family's cross-check kernel (A/B
+// measurements, tests).
+BatchPath batch_path(const ryd_batch_desc* d) {
+  const bool lind = d->evolution == RYD_EVOL_LINDBLAD, autom = d->method == RYD_METHOD_CHEBYSHEV;
+  // the protocols whose gate is a product of few propagators: LP square and bang-bang (few long
+  // segments), smooth JP (one propagator in the phase frame); LP shaped changes its amplitude
+  // every segment
+  const bool few = d->protocol != RYD_PROTO_LP_SHAPED;
+  // identical atoms under the auto method: the 16-lane DPP-row kernels
+  const bool rows16 = lind && autom && (d->flags & RYD_FLAG_SYMMETRIC_ATOMS) != 0;
+  if (d->method == RYD_METHOD_DOPRI5) return PATH_DOPRI5;
+  // dim 4, constant-|Omega| schedules: the triangle propagator kernel (ryd_dim4_prop.inc)
+  if (rows16 && d->dim == 4 && few && !is_off(getenv("RYD_DIM4_PROP"))) return PATH_DIM4_PROP;
+  // LP shaped: the state-vector kernel of ryd_shaped16.inc
+  if (rows16 && d->dim == 3 && !few && !is_off(getenv("RYD_SHAPED16"))) return PATH_SHAPED16;
+  // ryd_sym16.inc; the explicit RYD_METHOD_CHEB_SQUARING always runs the kernels below
+  if (rows16 && d->dim == 3 && few && !is_off(getenv("RYD_SYM16"))) return PATH_SYM16;
+  // the propagator kernel when asked for explicitly, or under the auto method for the
+  // few-propagator protocols; RYD_JP_SPLIT=0 keeps smooth JP in the fused kernel (the
+  // split-vs-fused bit-identity test)
+  const bool prop = lind && d->dim == 3 && (d->method == RYD_METHOD_CHEB_SQUARING || (autom && few));
+  if (prop && d->protocol == RYD_PROTO_SMOOTH_JP && !is_off(getenv("RYD_JP_SPLIT"))) return PATH_JP_SPLIT;
+  if (prop) return PATH_LINDBLAD_PROP;
+  if (lind) return PATH_LINDBLAD_CHEB;   // the per-lane state-vector Chebyshev kernel, dim 3 or 4
+  // kets under the auto method: the exact block-propagator kernel, one lane per point;
+  // RYD_METHOD_CHEB_VECTOR keeps the 4-lane Chebyshev state-vector kernel
+  if (autom && !is_off(getenv("RYD_KET_BLOCK"))) return PATH_KET_BLOCK;
+  return PATH_KET_CHEB;
+}
+
+// The paths with a store-free twin for summary-only launches: sym16 and the ket block kernel.
+// Every other one runs into a scratch buffer.  shaped16 and lindblad4_prop_kernel had twins
+// whose median did not lie below the storing kernel's range in every round (4.8 ms and 0.12 ms
+// of arithmetic per C2 launch against the 8 and 11.5 MB of stores; profiles/summary_only/), so
+// they were not kept.
+bool has_twin(BatchPath p) { return p == PATH_SYM16 || p == PATH_KET_BLOCK; }
 
 // RYD_S16_STORE64=1 makes the sym16 kernel form its output addresses per lane in 64 bits
 // for every launch (the form it takes anyway when a leading dimension is too large for a
@@ -2322,130 +2373,15 @@ int sym16_device_cus() {
   return c;
 }
 
-// LP shaped, identical atoms, the auto method: the 16-lane DPP-row state-vector kernel
-// (ryd_shaped16.inc); RYD_SHAPED16=0 keeps lindblad_cheb_kernel (the cross-check)
-bool use_shaped16(const ryd_batch_desc* d) {
-  const char* e = getenv("RYD_SHAPED16");
-  if (e && e[0] == '0') return false;
-  return d->dim == 3 && d->evolution == RYD_EVOL_LINDBLAD && d->method == RYD_METHOD_CHEBYSHEV &&
-         (d->flags & RYD_FLAG_SYMMETRIC_ATOMS) != 0 && d->protocol == RYD_PROTO_LP_SHAPED;
-}
-
-// dim 4, identical atoms, constant-|Omega| schedules: the triangle propagator kernel
-// (ryd_dim4_prop.inc); RYD_DIM4_PROP=0 keeps lindblad4_cheb_kernel (the cross-check)
-bool use_dim4_prop(const ryd_batch_desc* d) {
-  const char* e = getenv("RYD_DIM4_PROP");
-  if (e && e[0] == '0') return false;
-  return d->dim == 4 && d->evolution == RYD_EVOL_LINDBLAD && d->method == RYD_METHOD_CHEBYSHEV &&
-         (d->flags & RYD_FLAG_SYMMETRIC_ATOMS) != 0 &&
-         (d->protocol == RYD_PROTO_LP_SQUARE || d->protocol == RYD_PROTO_BANGBANG ||
-          d->protocol == RYD_PROTO_SMOOTH_JP);
-}
-
-// Kets under the default (auto) method: the exact block-propagator kernel, one lane per
-// point; RYD_METHOD_CHEB_VECTOR keeps the 4-lane Chebyshev state-vector kernel (the
-// cross-check), as does RYD_KET_BLOCK=0.
-bool use_ket_block(const ryd_batch_desc* d) {
-  const char* e = getenv("RYD_KET_BLOCK");
-  if (e && e[0] == '0') return false;
-  return d->evolution == RYD_EVOL_KET && d->method == RYD_METHOD_CHEBYSHEV;
-}
-
-KernelFn pick_kernel(const ryd_batch_desc* d) {
-  const bool sym = (d->flags & RYD_FLAG_SYMMETRIC_ATOMS) != 0;
-  if (d->dim == 4) {
-    if (d->evolution == RYD_EVOL_LINDBLAD) {
-      switch (d->protocol) {
-        case RYD_PROTO_LP_SQUARE:
-          return sym ? lindblad4_cheb_kernel<RYD_PROTO_LP_SQUARE, true> : lindblad4_cheb_kernel<RYD_PROTO_LP_SQUARE, false>;
-        case RYD_PROTO_LP_SHAPED:
-          return sym ? lindblad4_cheb_kernel<RYD_PROTO_LP_SHAPED, true> : lindblad4_cheb_kernel<RYD_PROTO_LP_SHAPED, false>;
-        case RYD_PROTO_BANGBANG:
-          return sym ? lindblad4_cheb_kernel<RYD_PROTO_BANGBANG, true> : lindblad4_cheb_kernel<RYD_PROTO_BANGBANG, false>;
-        case RYD_PROTO_SMOOTH_JP:
-          return sym ? lindblad4_cheb_kernel<RYD_PROTO_SMOOTH_JP, true> : lindblad4_cheb_kernel<RYD_PROTO_SMOOTH_JP, false>;
-      }
-    } else if (use_ket_block(d)) {
-      switch (d->protocol) {
-        case RYD_PROTO_LP_SQUARE: return ket_block_kernel<RYD_PROTO_LP_SQUARE, 4>;
-        case RYD_PROTO_LP_SHAPED: return ket_block_kernel<RYD_PROTO_LP_SHAPED, 4>;
-        case RYD_PROTO_BANGBANG: return ket_block_kernel<RYD_PROTO_BANGBANG, 4>;
-        case RYD_PROTO_SMOOTH_JP: return ket_block_kernel<RYD_PROTO_SMOOTH_JP, 4>;
-      }
-    } else {
-      switch (d->protocol) {
-        case RYD_PROTO_LP_SQUARE: return ket_cheb_kernel<RYD_PROTO_LP_SQUARE, 4>;
-        case RYD_PROTO_LP_SHAPED: return ket_cheb_kernel<RYD_PROTO_LP_SHAPED, 4>;
-        case RYD_PROTO_BANGBANG: return ket_cheb_kernel<RYD_PROTO_BANGBANG, 4>;
-        case RYD_PROTO_SMOOTH_JP: return ket_cheb_kernel<RYD_PROTO_SMOOTH_JP, 4>;
-      }
-    }
-    return nullptr;
-  }
-  if (use_propagator(d)) {
-    if (d->protocol == RYD_PROTO_LP_SQUARE)
-      return sym ? lindblad_prop_kernel<RYD_PROTO_LP_SQUARE, true> : lindblad_prop_kernel<RYD_PROTO_LP_SQUARE, false>;
-    if (d->protocol == RYD_PROTO_BANGBANG)
-      return sym ? lindblad_prop_kernel<RYD_PROTO_BANGBANG, true> : lindblad_prop_kernel<RYD_PROTO_BANGBANG, false>;
-    if (d->protocol == RYD_PROTO_SMOOTH_JP)
-      return sym ? lindblad_prop_kernel<RYD_PROTO_SMOOTH_JP, true> : lindblad_prop_kernel<RYD_PROTO_SMOOTH_JP, false>;
-    return sym ? lindblad_prop_kernel<RYD_PROTO_LP_SHAPED, true> : lindblad_prop_kernel<RYD_PROTO_LP_SHAPED, false>;
-  }
-  if (d->evolution == RYD_EVOL_LINDBLAD) {
-    switch (d->protocol) {
-      case RYD_PROTO_LP_SQUARE:
-        return sym ? lindblad_cheb_kernel<RYD_PROTO_LP_SQUARE, true> : lindblad_cheb_kernel<RYD_PROTO_LP_SQUARE, false>;
-      case RYD_PROTO_LP_SHAPED:
-        return sym ? lindblad_cheb_kernel<RYD_PROTO_LP_SHAPED, true> : lindblad_cheb_kernel<RYD_PROTO_LP_SHAPED, false>;
-      case RYD_PROTO_BANGBANG:
-        return sym ? lindblad_cheb_kernel<RYD_PROTO_BANGBANG, true> : lindblad_cheb_kernel<RYD_PROTO_BANGBANG, false>;
-      case RYD_PROTO_SMOOTH_JP:
-        return sym ? lindblad_cheb_kernel<RYD_PROTO_SMOOTH_JP, true> : lindblad_cheb_kernel<RYD_PROTO_SMOOTH_JP, false>;
-    }
-  } else if (d->evolution == RYD_EVOL_KET && use_ket_block(d)) {
-    switch (d->protocol) {
-      case RYD_PROTO_LP_SQUARE: return ket_block_kernel<RYD_PROTO_LP_SQUARE, 3>;
-      case RYD_PROTO_LP_SHAPED: return ket_block_kernel<RYD_PROTO_LP_SHAPED, 3>;
-      case RYD_PROTO_BANGBANG: return ket_block_kernel<RYD_PROTO_BANGBANG, 3>;
-      case RYD_PROTO_SMOOTH_JP: return ket_block_kernel<RYD_PROTO_SMOOTH_JP, 3>;
-    }
-  } else if (d->evolution == RYD_EVOL_KET) {
-    switch (d->protocol) {
-      case RYD_PROTO_LP_SQUARE: return ket_cheb_kernel<RYD_PROTO_LP_SQUARE, 3>;
-      case RYD_PROTO_LP_SHAPED: return ket_cheb_kernel<RYD_PROTO_LP_SHAPED, 3>;
-      case RYD_PROTO_BANGBANG: return ket_cheb_kernel<RYD_PROTO_BANGBANG, 3>;
-      case RYD_PROTO_SMOOTH_JP: return ket_cheb_kernel<RYD_PROTO_SMOOTH_JP, 3>;
-    }
-  }
-  return nullptr;
-}
-
-// the summary-only twin of the ket_block kernel pick_kernel() returns for d
-KernelFn pick_ket_block_nostate(const ryd_batch_desc* d) {
-  if (d->evolution != RYD_EVOL_KET || !use_ket_block(d)) return nullptr;
-  switch (d->protocol) {
-    case RYD_PROTO_LP_SQUARE:
-      return d->dim == 4 ? ket_block_nostate_kernel<RYD_PROTO_LP_SQUARE, 4> : ket_block_nostate_kernel<RYD_PROTO_LP_SQUARE, 3>;
-    case RYD_PROTO_LP_SHAPED:
-      return d->dim == 4 ? ket_block_nostate_kernel<RYD_PROTO_LP_SHAPED, 4> : ket_block_nostate_kernel<RYD_PROTO_LP_SHAPED, 3>;
-    case RYD_PROTO_BANGBANG:
-      return d->dim == 4 ? ket_block_nostate_kernel<RYD_PROTO_BANGBANG, 4> : ket_block_nostate_kernel<RYD_PROTO_BANGBANG, 3>;
-    case RYD_PROTO_SMOOTH_JP:
-      return d->dim == 4 ? ket_block_nostate_kernel<RYD_PROTO_SMOOTH_JP, 4> : ket_block_nostate_kernel<RYD_PROTO_SMOOTH_JP, 3>;
-  }
-  return nullptr;
-}
-
-// The descriptors launch_kernels<false> has a store-free kernel for: the dim-3 identical-atom
-// Lindblad path of the auto method for constant-|Omega| schedules (sym16) and the ket block
-// kernel.  Every other one (shaped16, the dim-4 propagator, the per-lane Chebyshev kernels,
-// lindblad_prop_kernel and the jp split, ket_cheb_kernel, the squaring method, DOPRI5) runs
-// into a scratch buffer.  shaped16 and lindblad4_prop_kernel had twins whose median did not lie
-// below the storing kernel's range in every round (4.8 ms and 0.12 ms of arithmetic per C2
-// launch against the 8 and 11.5 MB of stores; profiles/summary_only/), so they were not kept.
-bool has_nostate_kernel(const ryd_batch_desc* d) {
-  if (d->method == RYD_METHOD_DOPRI5) return false;
-  return use_sym16(d) || pick_ket_block_nostate(d) != nullptr;
+// the protocol and its n_steps / shape, for batch and trajectory descriptors alike
+int validate_protocol(int protocol, int n_steps, int shape) {
+  if (protocol < 0 || protocol > 3) return fail(RYD_ERR_INVALID, "bad protocol");
+  if (protocol == RYD_PROTO_LP_SHAPED && (n_steps < 2 || shape < 0 || shape > 3))
+    return fail(RYD_ERR_INVALID, "LP_SHAPED needs n_steps >= 2 and a valid shape");
+  if (protocol == RYD_PROTO_SMOOTH_JP && n_steps < 1) return fail(RYD_ERR_INVALID, "SMOOTH_JP needs n_steps >= 1");
+  if (protocol == RYD_PROTO_BANGBANG && (n_steps < 1 || n_steps > 8))
+    return fail(RYD_ERR_INVALID, "BANGBANG needs 1 <= n_steps (max segments) <= 8");
+  return RYD_OK;
 }
 
 // has_state = false: a summary-only call (null state pointer), whose ld_state is ignored
@@ -2465,25 +2401,12 @@ int validate(const ryd_batch_desc* d, int64_t n, int64_t ldp, int64_t lds, int64
   }
   if (d->method == RYD_METHOD_CHEB_SQUARING && d->evolution != RYD_EVOL_LINDBLAD)
     return fail(RYD_ERR_UNSUPPORTED, "squaring method is Lindblad-only");
-  if (d->protocol < 0 || d->protocol > 3) return fail(RYD_ERR_INVALID, "bad protocol");
   if (d->evolution != RYD_EVOL_LINDBLAD && d->evolution != RYD_EVOL_KET)
     return fail(RYD_ERR_INVALID, "bad evolution");
-  if (d->protocol == RYD_PROTO_LP_SHAPED && (d->n_steps < 2 || d->shape < 0 || d->shape > 3))
-    return fail(RYD_ERR_INVALID, "LP_SHAPED needs n_steps >= 2 and a valid shape");
-  if (d->protocol == RYD_PROTO_SMOOTH_JP && d->n_steps < 1)
-    return fail(RYD_ERR_INVALID, "SMOOTH_JP needs n_steps >= 1");
-  if (d->protocol == RYD_PROTO_BANGBANG && (d->n_steps < 1 || d->n_steps > 8))
-    return fail(RYD_ERR_INVALID, "BANGBANG needs 1 <= n_steps (max segments) <= 8");
+  if (int rc = validate_protocol(d->protocol, d->n_steps, d->shape)) return rc;
   if (n < 0) return fail(RYD_ERR_INVALID, "n < 0");
   if (ldp < n || (has_state && lds < 4 * n) || ldm < n) return fail(RYD_ERR_INVALID, "leading dimension too small");
   return RYD_OK;
-}
-
-// RYD_JP_SPLIT=0 keeps smooth JP in the fused lindblad_prop_kernel (A/B measurements and
-// the split-vs-fused bit-identity test); read at every launch
-bool jp_split_enabled() {
-  const char* e = getenv("RYD_JP_SPLIT");
-  return !(e && e[0] == '0');
 }
 
 // The jp workspace pool: a private stream-ordered pool per device, kept warm
@@ -2513,165 +2436,129 @@ hipMemPool_t jp_pool(int dev) {
 int launch_jp_split(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, double* ds,
                     int64_t lds, double* dm, int64_t ldm, uint32_t* dstat, hipStream_t stream) {
   const bool sym = (d->flags & RYD_FLAG_SYMMETRIC_ATOMS) != 0;
-  const int64_t blocks_a = (n + PPB - 1) / PPB, blocks_b = (n + FPB - 1) / FPB;
-  if (blocks_b > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
   int dev = 0;
   HIPCHK(hipGetDevice(&dev));
   hipMemPool_t pool = jp_pool(dev);
   if (!pool) return fail(RYD_ERR_ALLOC, "jp workspace pool creation failed");
   double* W = nullptr;
   HIPCHK(hipMallocFromPoolAsync((void**)&W, sizeof(double) * NC * NC * (size_t)n, pool, stream));
-  int ns = d->n_steps, sh = d->shape;
-  void* args_a[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&W, (void*)&dm, (void*)&ldm,
-                    (void*)&dstat, (void*)&ns, (void*)&sh};
-  const void* ka = sym ? (const void*)jp_rows_kernel<true> : (const void*)jp_rows_kernel<false>;
-  void* args_b[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&W, (void*)&ds, (void*)&lds,
-                    (void*)&dm, (void*)&ldm, (void*)&dstat, (void*)&ns};
+  const int ns = d->n_steps, sh = d->shape;
+  int rc = launch_typed(sym ? jp_rows_kernel<true> : jp_rows_kernel<false>, (n + PPB - 1) / PPB, BLOCK, 0, stream,
+                        dp, n, ldp, W, dm, ldm, dstat, ns, sh);
   // SYM holds 157 VGPRs (3 waves per SIMD; a 128 budget spills), the 4-output form 127
-  const void* kb = sym ? (const void*)jp_frame_kernel<3, true> : (const void*)jp_frame_kernel<4, false>;
-  hipError_t e = hipLaunchKernel(ka, dim3((unsigned)blocks_a), dim3(BLOCK), args_a, 0, stream);
-  if (e == hipSuccess) e = hipLaunchKernel(kb, dim3((unsigned)blocks_b), dim3(BLOCK), args_b, 0, stream);
+  if (!rc)
+    rc = launch_typed(sym ? jp_frame_kernel<3, true> : jp_frame_kernel<4, false>, (n + FPB - 1) / FPB, BLOCK, 0,
+                      stream, dp, n, ldp, W, ds, lds, dm, ldm, dstat, ns);
   hipError_t ef = hipFreeAsync(W, stream);          // on the error path too
-  if (e != hipSuccess) return fail(RYD_ERR_HIP, std::string("jp split launch: ") + hipGetErrorString(e));
+  if (rc) return rc;
   if (ef != hipSuccess) return fail(RYD_ERR_HIP, std::string("jp workspace free: ") + hipGetErrorString(ef));
   return RYD_OK;
 }
 
-// The kernel launch of one batch.  STATE = false (launch() alone passes it, with ds = NULL, and
-// only for a descriptor that has_nostate_kernel()) takes the summary-only twin of the kernel
-// the descriptor selects, with the same grid and arguments.
-template <bool STATE>
-int launch_kernels(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, double* ds, int64_t lds,
-                   double* dm, int64_t ldm, uint32_t* dstat, hipStream_t stream) {
-  if (d->method == RYD_METHOD_DOPRI5) {
-    using DFn = void (*)(const double*, int64_t, int64_t, double*, int64_t, double*, int64_t,
-                         uint32_t*, int, int, double, double, int64_t);
-    DFn f = nullptr;
-    switch (d->protocol) {
-      case RYD_PROTO_LP_SQUARE: f = lindblad_dopri5_kernel<RYD_PROTO_LP_SQUARE>; break;
-      case RYD_PROTO_LP_SHAPED: f = lindblad_dopri5_kernel<RYD_PROTO_LP_SHAPED>; break;
-      case RYD_PROTO_BANGBANG: f = lindblad_dopri5_kernel<RYD_PROTO_BANGBANG>; break;
-      default: f = lindblad_dopri5_kernel<RYD_PROTO_SMOOTH_JP>; break;
-    }
-    const int64_t blocks = (4 * n + DP_BLOCK - 1) / DP_BLOCK;
-    int ns = d->n_steps, sh = d->shape;
-    double rt = d->rtol, at = d->atol;
-    int64_t ms = d->max_steps;
-    void* args[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&ds, (void*)&lds, (void*)&dm,
-                    (void*)&ldm, (void*)&dstat, (void*)&ns, (void*)&sh, (void*)&rt, (void*)&at,
-                    (void*)&ms};
-    HIPCHK(hipLaunchKernel((const void*)f, dim3((unsigned)blocks), dim3(DP_BLOCK), args, 0, stream));
-    return RYD_OK;
-  }
-  if (use_dim4_prop(d)) {
-    using PFn = void (*)(const double*, int64_t, int64_t, double*, int64_t, double*, int64_t, uint32_t*,
-                         int, int);
-    PFn f = d->protocol == RYD_PROTO_LP_SQUARE ? lindblad4_prop_kernel<RYD_PROTO_LP_SQUARE>
-            : d->protocol == RYD_PROTO_SMOOTH_JP ? lindblad4_prop_kernel<RYD_PROTO_SMOOTH_JP>
-                                                  : lindblad4_prop_kernel<RYD_PROTO_BANGBANG>;
-    const int64_t blocks = (n + D4_PPB - 1) / D4_PPB;
-    if (blocks > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
-    int ns = d->n_steps, sh = d->shape;
-    void* args[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&ds, (void*)&lds, (void*)&dm,
-                    (void*)&ldm, (void*)&dstat, (void*)&ns, (void*)&sh};
-    HIPCHK(hipLaunchKernel((const void*)f, dim3((unsigned)blocks), dim3(D4_BLOCK), args, 0, stream));
-    return RYD_OK;
-  }
-  if (use_shaped16(d)) {
-    const int64_t blocks = (n + SH_PPW - 1) / SH_PPW;
-    if (blocks > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
-    int ns = d->n_steps, sh = d->shape;
-    void* args[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&ds, (void*)&lds, (void*)&dm,
-                    (void*)&ldm, (void*)&dstat, (void*)&ns, (void*)&sh};
-    HIPCHK(hipLaunchKernel((const void*)lindblad_shaped16_kernel<RYD_PROTO_LP_SHAPED>, dim3((unsigned)blocks),
-                           dim3(SH_BLOCK), args, 0, stream));
-    return RYD_OK;
-  }
-  if (use_sym16(d)) {
-    using SFn = void (*)(const double*, int64_t, int64_t, double*, int64_t, double*, int64_t, uint32_t*,
-                         int, int, int);
-    SFn f = d->protocol == RYD_PROTO_LP_SQUARE ? lindblad_sym16_kernel<RYD_PROTO_LP_SQUARE>
-            : d->protocol == RYD_PROTO_SMOOTH_JP ? lindblad_sym16_kernel<RYD_PROTO_SMOOTH_JP>
-                                                  : lindblad_sym16_kernel<RYD_PROTO_BANGBANG>;
-    if constexpr (!STATE)
-      f = d->protocol == RYD_PROTO_LP_SQUARE ? lindblad_sym16_nostate_kernel<RYD_PROTO_LP_SQUARE>
-          : d->protocol == RYD_PROTO_SMOOTH_JP ? lindblad_sym16_nostate_kernel<RYD_PROTO_SMOOTH_JP>
-                                                : lindblad_sym16_nostate_kernel<RYD_PROTO_BANGBANG>;
-    const int64_t blocks = (n + S16_PPW - 1) / S16_PPW;
-    if (blocks > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
-    int ns = d->n_steps, sh = d->shape;
-    // the output stores take a wave-uniform base plus a 32-bit lane byte offset where the
-    // largest one fits: 8 (15 + 3 lds) on the state rows, 8 (15 ldm + 3) on the summary
-    int st32 = sym16_store32_enabled() && lds >= 0 && ldm >= 0 && lds <= (0x1fffffffLL - 15) / 3 &&
-               ldm <= (0x1fffffffLL - 3) / 15;
-    const int bal = d->protocol == RYD_PROTO_LP_SQUARE ? sym16_balance_mode() : 0;
-    const int wtm = sym16_wt_mode();
-    if (wtm == -2) return fail(RYD_ERR_INVALID, "RYD_S16_WT must be 0, 1 or 3");
-    if (bal != 0) {
-      // the form is chosen first (forced, or the automatic rule on this device's CU count);
-      // the other switches are read, and checked, only by a launch that takes it
-      const int cus = sym16_device_cus();
-      S16Plan pl;
-      const bool planned = sym16_plan(n, cus, 0, &pl);
-      if (bal == 2 && !planned)
-        return fail(RYD_ERR_HIP, "RYD_S16_BALANCE=2: the device's compute-unit count is not available");
-      if (planned && (bal == 2 || pl.auto_on)) {
-        if (const char* eg = getenv("RYD_S16_BALANCE_GPC")) {
-          char* end = nullptr;
-          const long over = strtol(eg, &end, 10);
-          if (end == eg || *end != '\0' || over < 1 || over > S16_BAL_MAXW)
-            return fail(RYD_ERR_INVALID, "RYD_S16_BALANCE_GPC must be an integer from 1 to 16");
-          sym16_plan(n, cus, (int)over, &pl);
-        }
-        const char* eh = getenv("RYD_S16_BALANCE_NOHANDOFF");
-        if (pl.workgroups > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
-        using BFn = void (*)(const double*, int64_t, int64_t, double*, int64_t, double*, int64_t, uint32_t*,
-                             int, int, int, int, int);
-        // the first parameter load is one instruction per wave (load_point16_row) where its
-        // largest 32-bit lane offset, 8 (14 ldp + n), fits 31 bits: LP square reads columns
-        // 0 .. RYD_P_XI_IM = 14
-        static_assert(RYD_P_XI_IM == 14, "the largest LP-square parameter column");
-        const bool p32 = sym16_param32_enabled() && ldp <= (0x7fffffffLL / 8 - n) / 14;
-        BFn fb = p32 ? lindblad_sym16_kernel<RYD_PROTO_LP_SQUARE, 2> : lindblad_sym16_kernel<RYD_PROTO_LP_SQUARE, 1>;
-        if constexpr (!STATE)
-          fb = p32 ? lindblad_sym16_nostate_kernel<RYD_PROTO_LP_SQUARE, 2>
-                   : lindblad_sym16_nostate_kernel<RYD_PROTO_LP_SQUARE, 1>;
-        int gpc = pl.gpc, noh = eh && eh[0] == '1';
-        int wt = wtm >= 0 ? wtm : S16_WT_AUTO;
-        void* bargs[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&ds, (void*)&lds, (void*)&dm, (void*)&ldm,
-                         (void*)&dstat, (void*)&ns, (void*)&gpc, (void*)&st32, (void*)&noh, (void*)&wt};
-        HIPCHK(hipLaunchKernel((const void*)fb, dim3((unsigned)pl.workgroups), dim3(S16_BLOCK * pl.waves), bargs,
-                               0, stream));
-        return RYD_OK;
+// The sym16 path (ryd_sym16.inc): the one-wave kernel, or for LP square the CU-balanced form.
+// ds = NULL takes either one's summary-only twin, with the same grid and arguments.
+template <int PROTO>
+int launch_sym16(const double* dp, int64_t n, int64_t ldp, double* ds, int64_t lds, double* dm, int64_t ldm,
+                 uint32_t* dstat, int ns, int sh, hipStream_t stream) {
+  // the output stores take a wave-uniform base plus a 32-bit lane byte offset where the
+  // largest one fits: 8 (15 + 3 lds) on the state rows, 8 (15 ldm + 3) on the summary
+  const int st32 = sym16_store32_enabled() && lds >= 0 && ldm >= 0 && lds <= (0x1fffffffLL - 15) / 3 &&
+                   ldm <= (0x1fffffffLL - 3) / 15;
+  const int bal = PROTO == RYD_PROTO_LP_SQUARE ? sym16_balance_mode() : 0;
+  const int wtm = sym16_wt_mode();
+  if (wtm == -2) return fail(RYD_ERR_INVALID, "RYD_S16_WT must be 0, 1 or 3");
+  if (bal != 0) {
+    // the form is chosen first (forced, or the automatic rule on this device's CU count);
+    // the other switches are read, and checked, only by a launch that takes it
+    const int cus = sym16_device_cus();
+    S16Plan pl;
+    const bool planned = sym16_plan(n, cus, 0, &pl);
+    if (bal == 2 && !planned)
+      return fail(RYD_ERR_HIP, "RYD_S16_BALANCE=2: the device's compute-unit count is not available");
+    if (planned && (bal == 2 || pl.auto_on)) {
+      if (const char* eg = getenv("RYD_S16_BALANCE_GPC")) {
+        char* end = nullptr;
+        const long over = strtol(eg, &end, 10);
+        if (end == eg || *end != '\0' || over < 1 || over > S16_BAL_MAXW)
+          return fail(RYD_ERR_INVALID, "RYD_S16_BALANCE_GPC must be an integer from 1 to 16");
+        sym16_plan(n, cus, (int)over, &pl);
       }
+      const char* eh = getenv("RYD_S16_BALANCE_NOHANDOFF");
+      // the first parameter load is one instruction per wave (load_point16_row) where its
+      // largest 32-bit lane offset, 8 (14 ldp + n), fits 31 bits: LP square reads columns
+      // 0 .. RYD_P_XI_IM = 14
+      static_assert(RYD_P_XI_IM == 14, "the largest LP-square parameter column");
+      const bool p32 = sym16_param32_enabled() && ldp <= (0x7fffffffLL / 8 - n) / 14;
+      auto fb = p32 ? lindblad_sym16_kernel<RYD_PROTO_LP_SQUARE, 2> : lindblad_sym16_kernel<RYD_PROTO_LP_SQUARE, 1>;
+      if (!ds)
+        fb = p32 ? lindblad_sym16_nostate_kernel<RYD_PROTO_LP_SQUARE, 2>
+                 : lindblad_sym16_nostate_kernel<RYD_PROTO_LP_SQUARE, 1>;
+      const int noh = eh && eh[0] == '1', wt = wtm >= 0 ? wtm : S16_WT_AUTO;
+      return launch_typed(fb, pl.workgroups, S16_BLOCK * pl.waves, 0, stream, dp, n, ldp, ds, lds, dm, ldm, dstat,
+                          ns, pl.gpc, st32, noh, wt);
     }
-    // the one-wave kernels have plain stores only: a forced write-through cannot be honoured
-    if (wtm > 0) return fail(RYD_ERR_UNSUPPORTED, "RYD_S16_WT: write-through stores need the balanced launch form");
-    void* args[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&ds, (void*)&lds, (void*)&dm,
-                    (void*)&ldm, (void*)&dstat, (void*)&ns, (void*)&sh, (void*)&st32};
-    HIPCHK(hipLaunchKernel((const void*)f, dim3((unsigned)blocks), dim3(S16_BLOCK), args, 0, stream));
-    return RYD_OK;
   }
-  if (use_propagator(d) && d->protocol == RYD_PROTO_SMOOTH_JP && jp_split_enabled())
-    return launch_jp_split(d, dp, n, ldp, ds, lds, dm, ldm, dstat, stream);
-  KernelFn k = STATE ? pick_kernel(d) : pick_ket_block_nostate(d);
-  if (!k) return fail(RYD_ERR_UNSUPPORTED, "no kernel for this descriptor");
-  const int64_t blocks = use_propagator(d) ? (n + PPB - 1) / PPB
-                        : use_ket_block(d) ? (n + BLOCK - 1) / BLOCK : (4 * n + BLOCK - 1) / BLOCK;
-  if (blocks > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
-  int ns = d->n_steps, sh = d->shape;
-  void* args[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&ds, (void*)&lds, (void*)&dm,
-                  (void*)&ldm, (void*)&dstat, (void*)&ns, (void*)&sh};
-  HIPCHK(hipLaunchKernel((const void*)k, dim3((unsigned)blocks), dim3(BLOCK), args, 0, stream));
-  return RYD_OK;
+  // the one-wave kernels have plain stores only: a forced write-through cannot be honoured
+  if (wtm > 0) return fail(RYD_ERR_UNSUPPORTED, "RYD_S16_WT: write-through stores need the balanced launch form");
+  return launch_typed(ds ? lindblad_sym16_kernel<PROTO> : lindblad_sym16_nostate_kernel<PROTO>,
+                      (n + S16_PPW - 1) / S16_PPW, S16_BLOCK, 0, stream, dp, n, ldp, ds, lds, dm, ldm, dstat, ns, sh,
+                      st32);
 }
 
-// RYD_NOSTATE=0 sends every summary-only launch down the scratch-buffer path, the storing
-// kernels (A/B measurements and the cross-check of the store-free twins); read per launch
-bool nostate_enabled() {
-  const char* e = getenv("RYD_NOSTATE");
-  return !(e && e[0] == '0');
+// The kernel launch of one batch on the path batch_path() selected.  ds = NULL (launch() alone
+// passes it, and only on a path that has_twin()) takes the summary-only twin of the kernel
+// the descriptor selects, with the same grid and arguments.  Families built for three
+// protocols (or for LP shaped alone) are instantiated for those only.
+int launch_kernels(BatchPath path, const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, double* ds,
+                   int64_t lds, double* dm, int64_t ldm, uint32_t* dstat, hipStream_t stream) {
+  const bool sym = (d->flags & RYD_FLAG_SYMMETRIC_ATOMS) != 0, dim4 = d->dim == 4;
+  const int ns = d->n_steps, sh = d->shape;
+  // the ten arguments every kernel here starts with
+  auto go = [&](auto kernel, int64_t blocks, unsigned block, auto... more) {
+    return launch_typed(kernel, blocks, block, 0, stream, dp, n, ldp, ds, lds, dm, ldm, dstat, ns, sh,
+                        more...);
+  };
+  if (!ds && !has_twin(path)) return fail(RYD_ERR_UNSUPPORTED, "no kernel for this descriptor");
+  return with_protocol(d->protocol, [&](auto proto) -> int {
+    constexpr int P = decltype(proto)::value;
+    constexpr bool FEW = P != RYD_PROTO_LP_SHAPED;
+    KernelFn k = nullptr;
+    switch (path) {
+      case PATH_DOPRI5:
+        return go(lindblad_dopri5_kernel<P>, (4 * n + DP_BLOCK - 1) / DP_BLOCK, DP_BLOCK, d->rtol, d->atol,
+                  d->max_steps);
+      case PATH_DIM4_PROP:
+        if constexpr (FEW) return go(lindblad4_prop_kernel<P>, (n + D4_PPB - 1) / D4_PPB, D4_BLOCK);
+        break;
+      case PATH_SHAPED16:
+        if constexpr (!FEW) return go(lindblad_shaped16_kernel<P>, (n + SH_PPW - 1) / SH_PPW, SH_BLOCK);
+        break;
+      case PATH_SYM16:
+        if constexpr (FEW) return launch_sym16<P>(dp, n, ldp, ds, lds, dm, ldm, dstat, ns, sh, stream);
+        break;
+      case PATH_JP_SPLIT: return launch_jp_split(d, dp, n, ldp, ds, lds, dm, ldm, dstat, stream);
+      case PATH_LINDBLAD_PROP:
+        k = sym ? lindblad_prop_kernel<P, true> : lindblad_prop_kernel<P, false>;
+        return go(k, (n + PPB - 1) / PPB, BLOCK);
+      case PATH_LINDBLAD_CHEB:
+        k = dim4 ? (sym ? lindblad4_cheb_kernel<P, true> : lindblad4_cheb_kernel<P, false>)
+                 : (sym ? lindblad_cheb_kernel<P, true> : lindblad_cheb_kernel<P, false>);
+        return go(k, (4 * n + BLOCK - 1) / BLOCK, BLOCK);
+      case PATH_KET_BLOCK:
+        k = ds ? (dim4 ? ket_block_kernel<P, 4> : ket_block_kernel<P, 3>)
+               : (dim4 ? ket_block_nostate_kernel<P, 4> : ket_block_nostate_kernel<P, 3>);
+        return go(k, (n + BLOCK - 1) / BLOCK, BLOCK);
+      case PATH_KET_CHEB:
+        return go(dim4 ? ket_cheb_kernel<P, 4> : ket_cheb_kernel<P, 3>, (4 * n + BLOCK - 1) / BLOCK, BLOCK);
+    }
+    return fail(RYD_ERR_UNSUPPORTED, "no kernel for this descriptor");
+  });
 }
+
+// Whether a summary-only launch on this path runs the store-free twin.  RYD_NOSTATE=0 sends
+// every one down the scratch-buffer path, the storing kernels (A/B measurements and the
+// cross-check of the twins); read per launch.
+bool takes_twin(BatchPath p) { return has_twin(p) && !is_off(getenv("RYD_NOSTATE")); }
 
 // One batch on `stream`.  ds = NULL is a summary-only call, and this is the one place that
 // knows: the descriptor's store-free twin where it has one, otherwise the ordinary kernel into
@@ -2680,9 +2567,9 @@ bool nostate_enabled() {
 int launch(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, double* ds, int64_t lds,
            double* dm, int64_t ldm, uint32_t* dstat, hipStream_t stream) {
   if (n == 0) return RYD_OK;
-  if (ds) return launch_kernels<true>(d, dp, n, ldp, ds, lds, dm, ldm, dstat, stream);
-  if (nostate_enabled() && has_nostate_kernel(d))
-    return launch_kernels<false>(d, dp, n, ldp, nullptr, 0, dm, ldm, dstat, stream);
+  const BatchPath path = batch_path(d);
+  if (ds) return launch_kernels(path, d, dp, n, ldp, ds, lds, dm, ldm, dstat, stream);
+  if (takes_twin(path)) return launch_kernels(path, d, dp, n, ldp, nullptr, 0, dm, ldm, dstat, stream);
   const int sw = ryd_state_width(d->evolution, d->dim);
   if (sw <= 0) return fail(RYD_ERR_INVALID, "bad evolution");
   int dev = 0;
@@ -2691,7 +2578,7 @@ int launch(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, do
   if (!pool) return fail(RYD_ERR_ALLOC, "scratch state pool creation failed");
   double* W = nullptr;
   HIPCHK(hipMallocFromPoolAsync((void**)&W, sizeof(double) * (size_t)sw * 4 * (size_t)n, pool, stream));
-  const int rc = launch_kernels<true>(d, dp, n, ldp, W, 4 * n, dm, ldm, dstat, stream);
+  const int rc = launch_kernels(path, d, dp, n, ldp, W, 4 * n, dm, ldm, dstat, stream);
   hipError_t ef = hipFreeAsync(W, stream);           // on the error path too
   if (rc) return rc;
   if (ef != hipSuccess) return fail(RYD_ERR_HIP, std::string("scratch state free: ") + hipGetErrorString(ef));
@@ -2699,46 +2586,7 @@ int launch(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, do
 }
 
 // RYD_COH_PROP=0 selects coherence_cheb_kernel for every protocol (A/B and cross-check runs)
-bool coh_prop_enabled() {
-  const char* e = getenv("RYD_COH_PROP");
-  return !(e && e[0] == '0');
-}
-
-template <int PROTO, int DIM>
-int launch_coherences_proto(const double* dp, int64_t n, int64_t ldp, double* dc, int64_t ldc,
-                            uint32_t* dstat, int ns, int sh, hipStream_t stream) {
-  if (PROTO != RYD_PROTO_LP_SHAPED && coh_prop_enabled()) {   // one propagator per sector (ryd_coh_prop.inc)
-    const int64_t blocks = (n + CP_NR - 1) / CP_NR;
-    if (blocks > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
-    void* args[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&dc, (void*)&ldc, (void*)&dstat, (void*)&ns, (void*)&sh};
-    const void* k = DIM == 4 ? (const void*)coherence4_prop_kernel<PROTO> : (const void*)coherence_prop_kernel<PROTO>;
-    HIPCHK(hipLaunchKernel(k, dim3((unsigned)blocks), dim3(CP_BLOCK), args, 0, stream));
-    return RYD_OK;
-  }
-  const int64_t nb2 = (2 * n + BLOCK - 1) / BLOCK, nb1 = (n + BLOCK - 1) / BLOCK;
-  const int64_t b0 = nb2, b1 = 2 * nb2, b2 = 2 * nb2 + nb1, blocks = 2 * nb2 + 2 * nb1;
-  if (blocks > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
-  void* args[] = {(void*)&dp, (void*)&n, (void*)&ldp, (void*)&dc, (void*)&ldc, (void*)&dstat,
-                  (void*)&ns, (void*)&sh, (void*)&b0, (void*)&b1, (void*)&b2};
-  const void* k = DIM == 4 ? (const void*)coherence4_cheb_kernel<PROTO> : (const void*)coherence_cheb_kernel<PROTO>;
-  HIPCHK(hipLaunchKernel(k, dim3((unsigned)blocks), dim3(BLOCK), args, 0, stream));
-  return RYD_OK;
-}
-
-template <int DIM>
-int launch_coherences_dim(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, double* dc,
-                          int64_t ldc, uint32_t* dstat, hipStream_t stream) {
-  switch (d->protocol) {
-    case RYD_PROTO_LP_SQUARE:
-      return launch_coherences_proto<RYD_PROTO_LP_SQUARE, DIM>(dp, n, ldp, dc, ldc, dstat, d->n_steps, d->shape, stream);
-    case RYD_PROTO_LP_SHAPED:
-      return launch_coherences_proto<RYD_PROTO_LP_SHAPED, DIM>(dp, n, ldp, dc, ldc, dstat, d->n_steps, d->shape, stream);
-    case RYD_PROTO_BANGBANG:
-      return launch_coherences_proto<RYD_PROTO_BANGBANG, DIM>(dp, n, ldp, dc, ldc, dstat, d->n_steps, d->shape, stream);
-    default:
-      return launch_coherences_proto<RYD_PROTO_SMOOTH_JP, DIM>(dp, n, ldp, dc, ldc, dstat, d->n_steps, d->shape, stream);
-  }
-}
+bool coh_prop_enabled() { return !is_off(getenv("RYD_COH_PROP")); }
 
 // The coherence sectors of one batch (one launch); status is cleared first and each
 // sector ORs its bits in.  dim 4: the kernels of ryd_coh4_prop.inc.
@@ -2746,8 +2594,18 @@ int launch_coherences(const ryd_batch_desc* d, const double* dp, int64_t n, int6
                       int64_t ldc, uint32_t* dstat, hipStream_t stream) {
   if (n == 0) return RYD_OK;
   HIPCHK(hipMemsetAsync(dstat, 0, sizeof(uint32_t) * n, stream));
-  return d->dim == 4 ? launch_coherences_dim<4>(d, dp, n, ldp, dc, ldc, dstat, stream)
-                     : launch_coherences_dim<3>(d, dp, n, ldp, dc, ldc, dstat, stream);
+  const bool dim4 = d->dim == 4;
+  const int ns = d->n_steps, sh = d->shape;
+  return with_protocol(d->protocol, [&](auto proto) {
+    constexpr int P = decltype(proto)::value;
+    if (P != RYD_PROTO_LP_SHAPED && coh_prop_enabled())   // one propagator per sector (ryd_coh_prop.inc)
+      return launch_typed(dim4 ? coherence4_prop_kernel<P> : coherence_prop_kernel<P>, (n + CP_NR - 1) / CP_NR,
+                          CP_BLOCK, 0, stream, dp, n, ldp, dc, ldc, dstat, ns, sh);
+    const int64_t nb2 = (2 * n + BLOCK - 1) / BLOCK, nb1 = (n + BLOCK - 1) / BLOCK;
+    const int64_t b0 = nb2, b1 = 2 * nb2, b2 = 2 * nb2 + nb1;
+    return launch_typed(dim4 ? coherence4_cheb_kernel<P> : coherence_cheb_kernel<P>, 2 * nb2 + 2 * nb1, BLOCK, 0,
+                        stream, dp, n, ldp, dc, ldc, dstat, ns, sh, b0, b1, b2);
+  });
 }
 
 int validate_coherences(const ryd_batch_desc* d, int64_t n, int64_t ldp, int64_t ldc) {
@@ -2783,6 +2641,47 @@ struct LaunchTimer {
     if (e1) (void)hipEventDestroy(e1);
   }
 };
+
+// What the *_device entry points share: the slot check, the entry point's own validation
+// (`check`), the slot's device, the caller's stream or else the slot's, and `go(stream)`
+// between HIP events where elapsed_ms is asked for.
+template <typename Check, typename Go>
+int on_slot(ryd_handle* h, int slot, void* stream, float* elapsed_ms, Check&& check, Go&& go) {
+  if (!h || slot < 0 || slot >= (int)h->dev.size()) return fail(RYD_ERR_INVALID, "bad handle/slot");
+  int rc = check();
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(h->dev[slot]));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream[slot];
+  LaunchTimer timer;
+  if (elapsed_ms && (rc = timer.start(s))) return rc;
+  if ((rc = go(s))) return rc;
+  return elapsed_ms ? timer.stop(s, elapsed_ms) : RYD_OK;
+}
+
+// The ryd_stats of a host-form call: the timings, and the sums over the batch of the two
+// summary rows that count iterations (summary = NULL: none, as for coherences).
+void fill_stats(ryd_stats* st, const ryd_handle* h, double kms, double hms, double dms, const double* summary,
+                int64_t ld, int64_t n, int row_useful, int row_exec) {
+  if (!st) return;
+  double u = 0.0, x = 0.0;
+  for (int64_t i = 0; summary && i < n; ++i) {
+    u += summary[(int64_t)row_useful * ld + i];
+    x += summary[(int64_t)row_exec * ld + i];
+  }
+  *st = {kms, hms, dms, u, x, (int)h->dev.size(), 0};
+}
+
+// ryd_memcpy_h2d / ryd_memcpy_d2h: a blocking copy on the slot's stream
+int slot_memcpy(ryd_handle* h, int slot, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+  if (!h || slot < 0 || slot >= (int)h->dev.size()) return fail(RYD_ERR_INVALID, "bad args");
+  HIPCHK(hipSetDevice(h->dev[slot]));
+  // the slot's earlier work first: a copy to or from pageable memory is not reliably
+  // ordered behind the kernels already on the stream
+  HIPCHK(hipStreamSynchronize(h->stream[slot]));
+  HIPCHK(hipMemcpyAsync(dst, src, bytes, kind, h->stream[slot]));
+  HIPCHK(hipStreamSynchronize(h->stream[slot]));
+  return RYD_OK;
+}
 
 // One output array of a partitioned run: `rows` rows of `per_point` doubles per point.
 struct HostOut {
@@ -3232,25 +3131,11 @@ int ryd_free(ryd_handle* h, int slot, void* p) {
 }
 
 int ryd_memcpy_h2d(ryd_handle* h, int slot, void* dst, const void* src, size_t bytes) {
-  if (!h || slot < 0 || slot >= (int)h->dev.size()) return fail(RYD_ERR_INVALID, "bad args");
-  HIPCHK(hipSetDevice(h->dev[slot]));
-  // the slot's earlier work first: a copy to or from pageable memory is not reliably
-  // ordered behind the kernels already on the stream
-  HIPCHK(hipStreamSynchronize(h->stream[slot]));
-  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream[slot]));
-  HIPCHK(hipStreamSynchronize(h->stream[slot]));
-  return RYD_OK;
+  return slot_memcpy(h, slot, dst, src, bytes, hipMemcpyHostToDevice);
 }
 
 int ryd_memcpy_d2h(ryd_handle* h, int slot, void* dst, const void* src, size_t bytes) {
-  if (!h || slot < 0 || slot >= (int)h->dev.size()) return fail(RYD_ERR_INVALID, "bad args");
-  HIPCHK(hipSetDevice(h->dev[slot]));
-  // the slot's earlier work first: a copy to or from pageable memory is not reliably
-  // ordered behind the kernels already on the stream
-  HIPCHK(hipStreamSynchronize(h->stream[slot]));
-  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream[slot]));
-  HIPCHK(hipStreamSynchronize(h->stream[slot]));
-  return RYD_OK;
+  return slot_memcpy(h, slot, dst, src, bytes, hipMemcpyDeviceToHost);
 }
 
 int ryd_last_timeline(ryd_handle* h, double* out, int64_t cap) {
@@ -3294,23 +3179,22 @@ int ryd_synchronize(ryd_handle* h) {
   return RYD_OK;
 }
 
+int ryd_batch_path(const ryd_batch_desc* desc, int has_state) {
+  if (int rc = validate(desc, 0, 0, 0, 0)) return rc;
+  const BatchPath path = batch_path(desc);
+  return !has_state && takes_twin(path) ? path | RYD_PATH_NOSTATE : path;
+}
+
 int ryd_run_batch_device(ryd_handle* h, int slot, const ryd_batch_desc* desc, const double* d_params,
                          int64_t n, int64_t ld_params, double* d_state, int64_t ld_state,
                          double* d_summary, int64_t ld_summary, uint32_t* d_status, void* stream,
                          float* elapsed_ms) {
-  if (!h || slot < 0 || slot >= (int)h->dev.size()) return fail(RYD_ERR_INVALID, "bad handle/slot");
-  int rc = validate(desc, n, ld_params, ld_state, ld_summary, d_state != nullptr);
-  if (rc) return rc;
-  HIPCHK(hipSetDevice(h->dev[slot]));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream[slot];
-  LaunchTimer timer;
-  if (elapsed_ms) {
-    rc = timer.start(s);
-    if (rc) return rc;
-  }
-  rc = launch(desc, d_params, n, ld_params, d_state, ld_state, d_summary, ld_summary, d_status, s);
-  if (rc) return rc;
-  return elapsed_ms ? timer.stop(s, elapsed_ms) : RYD_OK;
+  return on_slot(
+      h, slot, stream, elapsed_ms,
+      [&] { return validate(desc, n, ld_params, ld_state, ld_summary, d_state != nullptr); },
+      [&](hipStream_t s) {
+        return launch(desc, d_params, n, ld_params, d_state, ld_state, d_summary, ld_summary, d_status, s);
+      });
 }
 
 int ryd_run_batch(ryd_handle* h, const ryd_batch_desc* desc, const double* params, int64_t n,
@@ -3336,20 +3220,7 @@ int ryd_run_batch(ryd_handle* h, const ryd_batch_desc* desc, const double* param
       },
       kms, hms, dms);
   if (rc) return rc;
-  if (stats) {
-    stats->kernel_ms = kms;
-    stats->h2d_ms = hms;
-    stats->d2h_ms = dms;
-    double u = 0.0, x = 0.0;
-    for (int64_t i = 0; i < n; ++i) {
-      u += out_summary[(int64_t)RYD_S_NMV_USEFUL * ld_summary + i];
-      x += out_summary[(int64_t)RYD_S_NMV_EXEC * ld_summary + i];
-    }
-    stats->matvec_useful = u;
-    stats->matvec_exec = x;
-    stats->n_devices = (int)h->dev.size();
-    stats->reserved = 0;
-  }
+  fill_stats(stats, h, kms, hms, dms, out_summary, ld_summary, n, RYD_S_NMV_USEFUL, RYD_S_NMV_EXEC);
   return RYD_OK;
 }
 
@@ -3368,14 +3239,7 @@ int ryd_run_coherences(ryd_handle* h, const ryd_batch_desc* desc, const double* 
           hipStream_t s) { return launch_coherences(desc, dp, cnt, ldp, o[0], cnt, dst, s); },
       kms, hms, dms);
   if (rc) return rc;
-  if (stats) {
-    stats->kernel_ms = kms;
-    stats->h2d_ms = hms;
-    stats->d2h_ms = dms;
-    stats->matvec_useful = stats->matvec_exec = 0.0;
-    stats->n_devices = (int)h->dev.size();
-    stats->reserved = 0;
-  }
+  fill_stats(stats, h, kms, hms, dms, nullptr, 0, 0, 0, 0);
   return RYD_OK;
 }
 
@@ -3403,20 +3267,7 @@ int ryd_run_trajectories(ryd_handle* h, const ryd_traj_desc* desc, const double*
       },
       kms, hms, dms);
   if (rc) return rc;
-  if (stats) {
-    stats->kernel_ms = kms;
-    stats->h2d_ms = hms;
-    stats->d2h_ms = dms;
-    double u = 0.0, x = 0.0;
-    for (int64_t i = 0; i < n; ++i) {
-      u += out_summary[(int64_t)RYD_TS_ITER_USEFUL * ld_summary + i];
-      x += out_summary[(int64_t)RYD_TS_ITER_EXEC * ld_summary + i];
-    }
-    stats->matvec_useful = u;
-    stats->matvec_exec = x;
-    stats->n_devices = (int)h->dev.size();
-    stats->reserved = 0;
-  }
+  fill_stats(stats, h, kms, hms, dms, out_summary, ld_summary, n, RYD_TS_ITER_USEFUL, RYD_TS_ITER_EXEC);
   return RYD_OK;
 }
 
@@ -3440,57 +3291,36 @@ int ryd_run_trajectories_device(ryd_handle* h, int slot, const ryd_traj_desc* de
                                 int64_t ld_rho, double* d_se, int64_t ld_se, double* d_summary,
                                 int64_t ld_summary, double* d_records, uint32_t* d_status, void* stream,
                                 float* elapsed_ms) {
-  if (!h || slot < 0 || slot >= (int)h->dev.size()) return fail(RYD_ERR_INVALID, "bad handle/slot");
-  int rc = validate_traj(desc, n, ld_params);
-  if (rc) return rc;
-  if (ld_rho < RYD_T_RHO_WIDTH || ld_se < RYD_T_SE_WIDTH || ld_summary < n || point_offset < 0)
-    return fail(RYD_ERR_INVALID, "leading dimension too small or negative point_offset");
-  HIPCHK(hipSetDevice(h->dev[slot]));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream[slot];
-  LaunchTimer timer;
-  if (elapsed_ms) {
-    rc = timer.start(s);
-    if (rc) return rc;
-  }
-  rc = launch_traj(desc, d_params, n, ld_params, point_offset, d_rho, ld_rho, d_se, ld_se, d_summary, ld_summary,
-                   d_records, d_status, s);
-  if (rc) return rc;
-  return elapsed_ms ? timer.stop(s, elapsed_ms) : RYD_OK;
+  return on_slot(
+      h, slot, stream, elapsed_ms,
+      [&] {
+        if (int rc = validate_traj(desc, n, ld_params)) return rc;
+        if (ld_rho < RYD_T_RHO_WIDTH || ld_se < RYD_T_SE_WIDTH || ld_summary < n || point_offset < 0)
+          return fail(RYD_ERR_INVALID, "leading dimension too small or negative point_offset");
+        return RYD_OK;
+      },
+      [&](hipStream_t s) {
+        return launch_traj(desc, d_params, n, ld_params, point_offset, d_rho, ld_rho, d_se, ld_se, d_summary,
+                           ld_summary, d_records, d_status, s);
+      });
 }
 
 int ryd_run_coherences_device(ryd_handle* h, int slot, const ryd_batch_desc* desc, const double* d_params,
                               int64_t n, int64_t ld_params, double* d_coh, int64_t ld_coh,
                               uint32_t* d_status, void* stream, float* elapsed_ms) {
-  if (!h || slot < 0 || slot >= (int)h->dev.size()) return fail(RYD_ERR_INVALID, "bad handle/slot");
-  int rc = validate_coherences(desc, n, ld_params, ld_coh);
-  if (rc) return rc;
-  HIPCHK(hipSetDevice(h->dev[slot]));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream[slot];
-  LaunchTimer timer;
-  if (elapsed_ms) {
-    rc = timer.start(s);
-    if (rc) return rc;
-  }
-  rc = launch_coherences(desc, d_params, n, ld_params, d_coh, ld_coh, d_status, s);
-  if (rc) return rc;
-  return elapsed_ms ? timer.stop(s, elapsed_ms) : RYD_OK;
+  return on_slot(
+      h, slot, stream, elapsed_ms, [&] { return validate_coherences(desc, n, ld_params, ld_coh); },
+      [&](hipStream_t s) { return launch_coherences(desc, d_params, n, ld_params, d_coh, ld_coh, d_status, s); });
 }
 
 int ryd_derive_device(ryd_handle* h, int slot, const ryd_derive_desc* desc, const double* d_in, int64_t ld_in,
                       int64_t n, double* d_params, int64_t ld_params, uint32_t* d_warn, double* d_diag,
                       int64_t ld_diag, void* stream, float* elapsed_ms) {
-  if (!h || slot < 0 || slot >= (int)h->dev.size()) return fail(RYD_ERR_INVALID, "bad handle/slot");
-  HIPCHK(hipSetDevice(h->dev[slot]));
-  hipStream_t s = stream ? (hipStream_t)stream : h->stream[slot];
-  LaunchTimer timer;
-  int rc;
-  if (elapsed_ms) {
-    rc = timer.start(s);
-    if (rc) return rc;
-  }
-  rc = launch_derive(desc, d_in, ld_in, n, d_params, ld_params, d_warn, d_diag, ld_diag, s);
-  if (rc) return rc;
-  return elapsed_ms ? timer.stop(s, elapsed_ms) : RYD_OK;
+  return on_slot(
+      h, slot, stream, elapsed_ms, [] { return RYD_OK; },      // launch_derive validates
+      [&](hipStream_t s) {
+        return launch_derive(desc, d_in, ld_in, n, d_params, ld_params, d_warn, d_diag, ld_diag, s);
+      });
 }
 
 int ryd_derive(ryd_handle* h, const ryd_derive_desc* desc, const double* in, int64_t n_cols, int64_t ld_in,

@@ -30,7 +30,7 @@ constexpr int SH_PPW = 4;
 constexpr int SH_BUF = NS * 16 + 5 * 5;        // >= 4 x 25 (outputs) and 2 x 20 (frame stage)
 constexpr int SH_KMAX = 64;
 constexpr double SH_XSUB = 20.0;               // largest series argument per (sub-)step: cheb_terms <= 46                    // series terms per segment (x <= ~40; beyond: the
-                                               // generic kernel -- see use_shaped16's caller)
+                                               // generic kernel -- see batch_path())
 
 // coordinate s of Q R Q^T on the 15-coordinate triangle (Q rotates (ex, ey) = (3, 4) of each
 // atom: x' = c x + sn y, y' = -sn x + c y), read from the stage u

@@ -860,13 +860,7 @@ int t_launch_proto(const TrajArgs& ta, hipStream_t stream) {
 int validate_traj(const ryd_traj_desc* d, int64_t n, int64_t ldp) {
   if (!d) return fail(RYD_ERR_INVALID, "desc is NULL");
   if (d->abi_version != RYD_ABI_VERSION) return fail(RYD_ERR_INVALID, "abi_version mismatch");
-  if (d->protocol < 0 || d->protocol > 3) return fail(RYD_ERR_INVALID, "bad protocol");
-  if (d->protocol == RYD_PROTO_LP_SHAPED && (d->n_steps < 2 || d->shape < 0 || d->shape > 3))
-    return fail(RYD_ERR_INVALID, "LP_SHAPED needs n_steps >= 2 and a valid shape");
-  if (d->protocol == RYD_PROTO_SMOOTH_JP && d->n_steps < 1)
-    return fail(RYD_ERR_INVALID, "SMOOTH_JP needs n_steps >= 1");
-  if (d->protocol == RYD_PROTO_BANGBANG && (d->n_steps < 1 || d->n_steps > 8))
-    return fail(RYD_ERR_INVALID, "BANGBANG needs 1 <= n_steps (max segments) <= 8");
+  if (int rc = validate_protocol(d->protocol, d->n_steps, d->shape)) return rc;
   if (d->n_traj < T_WAVE || d->n_traj % T_WAVE != 0 || d->n_traj > (1 << 20))
     return fail(RYD_ERR_INVALID, "n_traj must be a positive multiple of 64 (<= 2^20)");
   if ((d->flags & ~RYD_T_FLAG_LANES) != 0u)
@@ -918,10 +912,6 @@ int launch_traj(const ryd_traj_desc* d, const double* dp, int64_t n, int64_t ldp
   ta.arrive = nullptr;
   ta.seed = d->seed;
   for (int e = 0; e < T_NV; ++e) ta.psi0[e] = d->psi0[e];
-  switch (d->protocol) {
-    case RYD_PROTO_LP_SQUARE: return t_launch_proto<RYD_PROTO_LP_SQUARE>(ta, stream);
-    case RYD_PROTO_LP_SHAPED: return t_launch_proto<RYD_PROTO_LP_SHAPED>(ta, stream);
-    case RYD_PROTO_BANGBANG: return t_launch_proto<RYD_PROTO_BANGBANG>(ta, stream);
-    default: return t_launch_proto<RYD_PROTO_SMOOTH_JP>(ta, stream);
-  }
+  return with_protocol(d->protocol,
+                       [&](auto proto) { return t_launch_proto<decltype(proto)::value>(ta, stream); });
 }

@@ -247,6 +247,16 @@ def sym16_balance_plan(n: int, cus: int = 256, gpc: int = 0) -> Dict[str, Any]:
                 role=role.reshape(shape), job=job.reshape(shape), present=present.reshape(shape).astype(bool))
 
 
+def batch_path(desc: N.BatchDesc, states: bool = True) -> int:
+    """The kernel family a batch call launches for ``desc`` (``N.PATH``), under the environment
+    switches as they stand now; ``states=False`` asks about a summary-only call, and
+    ``N.PATH["NOSTATE"]`` is then OR-ed in where it runs the store-free twin.  Host code only."""
+    rc = N.load().ryd_batch_path(ctypes.byref(desc), 1 if states else 0)
+    if rc < 0:
+        N.check(rc)
+    return rc
+
+
 def device_count() -> int:
     """GPUs visible to the HIP runtime (ryd_device_count)."""
     lib = N.load()

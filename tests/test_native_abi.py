@@ -34,6 +34,9 @@ def test_header_constants_match_binding():
     assert int(defs["RYD_NCOH"]) == N.NCOH
     for k, v in N.PROTO.items():
         assert int(defs["RYD_PROTO_" + k.upper()]) == v
+    for k, v in N.PATH.items():
+        assert int(defs["RYD_PATH_" + k]) == v
+    assert len([k for k in defs if k.startswith("RYD_PATH_")]) == len(N.PATH)
     assert ctypes.sizeof(N.BatchDesc) == 56 and ctypes.sizeof(N.Stats) == 48
     for k, v in N.T.items():
         assert int(defs["RYD_T_" + k]) == v
