@@ -351,6 +351,66 @@ int ryd_run_batch_device(ryd_handle* h, int slot, const ryd_batch_desc* desc,
                          double* d_summary, int64_t ld_summary,
                          uint32_t* d_status, void* stream, float* elapsed_ms);
 
+/* ---- custom pulse schedules: piecewise-constant amplitude, phase, detuning ----
+ * The caller's own pulse as a table of n_seg segments per point (or one table for every
+ * point), where the four protocols above generate theirs on the device from per-point
+ * scalars: a measured pulse with edges, a phase profile that is no sinusoid, a chirped
+ * detuning, the piecewise-constant parameterisation of a pulse optimiser.  Segment s of
+ * point i is  Omega_s = a_s Omega e^{i phi_s},  Delta_s = delta_s Omega,  dt_s = x_s / Omega
+ * with Omega = the point's RYD_P_OMEGA.  The table is point-major,
+ *     sched[i * ld_sched + f * n_seg + s],   f = RYD_SC_X .. RYD_SC_DELTA,
+ * ld_sched >= RYD_SC_NFIELD * n_seg; with RYD_SCHED_SHARED in desc->flags one row of
+ * RYD_SC_NFIELD * n_seg doubles serves every point and ld_sched is ignored.
+ * Parameter columns read: RYD_P_OMEGA, V, DELTA1 and the eight rate columns; RYD_P_DELTA,
+ * TAU, XI_*, AREA_CORR and the smooth-JP and bang-bang columns are ignored (and not checked).
+ * Lindblad, dim 3, identical atoms (RYD_FLAG_SYMMETRIC_ATOMS is required): one kernel,
+ * lindblad_sched16_kernel, four points per wave.  It builds one propagator per run of equal
+ * (a_s Omega, delta_s Omega, x_s / Omega) -- compared exactly, so a phase-only schedule with
+ * equal segments costs one build and one state update per segment, as smooth JP does -- and
+ * carries the states through the phase changes in the rotating frame.  A segment of duration
+ * zero is skipped; a_s = 0 with x_s > 0 is free evolution under V, delta_s, DELTA1 and the rates.
+ * Outputs: exactly those of ryd_run_batch for RYD_EVOL_LINDBLAD, dim 3 (25 state rows per
+ * (point, input), the RYD_S_* summary, the status bits); a NULL state pointer is a
+ * summary-only run (store-free twin of the kernel; summary and status bit for bit).
+ * RYD_S_NSQUARE / NMV_USEFUL / NMV_EXEC accumulate over the point's builds.  Per point:
+ * RYD_STATUS_BAD_INPUT for Omega <= 0, a negative rate, a non-finite scalar or table entry,
+ * x_s < 0 or a_s < 0 (the point's rows then hold the untouched inputs, as for the protocols
+ * above); RYD_STATUS_STEP_CAP for a segment beyond the propagator build's argument cap.
+ * Refused before any GPU call: NULL desc / table / handle, abi_version, n_seg outside
+ * 1 .. RYD_SCHED_MAX_SEG, unknown flag bits, a leading dimension too small (RYD_ERR_INVALID);
+ * dim != 3, RYD_FLAG_SYMMETRIC_ATOMS missing (RYD_ERR_UNSUPPORTED). */
+#define RYD_SC_X       0   /* x_s = Omega dt_s >= 0 (the convention of the bang-bang switching times) */
+#define RYD_SC_AMP     1   /* a_s = Omega_s / Omega >= 0                                  */
+#define RYD_SC_PHASE   2   /* phi_s, radians                                             */
+#define RYD_SC_DELTA   3   /* delta_s = Delta_s / Omega, signed                          */
+#define RYD_SC_NFIELD  4
+#define RYD_SCHED_SHARED  2u   /* ryd_sched_desc.flags: one table row for every point    */
+#define RYD_SCHED_MAX_SEG 4096
+typedef struct ryd_sched_desc {
+    int32_t abi_version;     /* = RYD_ABI_VERSION */
+    int32_t dim;             /* 3 */
+    int32_t n_seg;           /* segments per point, 1 .. RYD_SCHED_MAX_SEG */
+    uint32_t flags;          /* RYD_FLAG_SYMMETRIC_ATOMS (required) | RYD_SCHED_SHARED */
+} ryd_sched_desc;
+
+/* Host buffers; partitions, stages and overlaps like ryd_run_batch (each slot's rows of
+ * the table travel as one contiguous block, or the shared row).  out_state may be NULL. */
+int ryd_run_schedule(ryd_handle* h, const ryd_sched_desc* desc,
+                     const double* params, int64_t n, int64_t ld_params,
+                     const double* sched, int64_t ld_sched,
+                     double* out_state, int64_t ld_state,
+                     double* out_summary, int64_t ld_summary,
+                     uint32_t* out_status, ryd_stats* stats);
+/* Device buffers on slot `slot` (d_sched: (n - 1) * ld_sched + RYD_SC_NFIELD * n_seg doubles,
+ * or RYD_SC_NFIELD * n_seg when shared); stream / elapsed_ms as ryd_run_batch_device.
+ * d_state may be NULL. */
+int ryd_run_schedule_device(ryd_handle* h, int slot, const ryd_sched_desc* desc,
+                            const double* d_params, int64_t n, int64_t ld_params,
+                            const double* d_sched, int64_t ld_sched,
+                            double* d_state, int64_t ld_state,
+                            double* d_summary, int64_t ld_summary,
+                            uint32_t* d_status, void* stream, float* elapsed_ms);
+
 /* Process-map coherences (layout above).  Chebyshev state-vector method; any
  * protocol, either evolution value (rates may be zero).  Host-buffer form
  * range-partitions like ryd_run_batch; status bits as ryd_run_batch. */

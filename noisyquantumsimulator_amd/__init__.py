@@ -11,8 +11,8 @@ is missing -- there is no CPU fallback.
 """
 from .constants import A0, C, E_CHARGE, EPS0, HBAR, KB, MU_B, RY_JOULES
 from .configurations import (AtomicConfiguration, JPSimulationInputs, LaserParameters,
-                             LPSimulationInputs, NoiseSourceConfig, SmoothJPSimulationInputs,
-                             TwoPhotonExcitationConfig)
+                             LPSimulationInputs, NoiseSourceConfig, PulseScheduleInputs,
+                             SmoothJPSimulationInputs, TwoPhotonExcitationConfig)
 from .protocols import (JP_BANGBANG_OMEGA_TAU, JP_BANGBANG_PHASES, JP_BANGBANG_SWITCHING_TIMES,
                         LP_DELTA_OVER_OMEGA_DEFAULT, LP_OMEGA_TAU_DEFAULT, LP_XI_DEFAULT,
                         SMOOTH_JP_DEFAULTS as SMOOTH_JP_PARAMS, compute_phase_shift_xi)
@@ -25,6 +25,7 @@ from .optimize_cz_gate import (JP_PHASES_DEFAULT, JP_SWITCHING_TIMES_DEFAULT, Ap
 from .optimization import (EvaluatedPoint, ExplorationResult, HardwareOptimizationResult,
                            combine_explorations, explore_parameter_space, optimize_CZ_parameters)
 from .engine import Engine, DeviceBatch
+from . import pulse_schedules
 from .noise_models import gate_process_maps
 from .calibration import calibrate_cz, load_calibration, write_calibration
 
@@ -47,4 +48,6 @@ __all__ = [
     "HBAR", "EPS0", "C", "E_CHARGE", "A0", "KB", "MU_B", "RY_JOULES",
     # engine, process maps, calibration files (beyond the reference)
     "Engine", "DeviceBatch", "gate_process_maps", "calibrate_cz", "write_calibration", "load_calibration",
+    # the caller's own pulse as a table of piecewise-constant segments (beyond the reference)
+    "PulseScheduleInputs", "pulse_schedules",
 ]

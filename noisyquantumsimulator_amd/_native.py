@@ -48,6 +48,12 @@ STATE_WIDTH_DIM = {3: STATE_WIDTH, 4: {"lindblad": 36, "ket": 32}}
 C = dict(K0=0, K1=8, K2=16, K3=18)
 NCOH = 20
 
+# custom pulse schedules (ryd_run_schedule): table fields, the shared-table flag, the segment cap
+SC = dict(X=0, AMP=1, PHASE=2, DELTA=3)
+SC_NFIELD = 4
+RYD_SCHED_SHARED = 2
+SCHED_MAX_SEG = 4096
+
 # three-atom quantum-jump trajectories (ryd_run_trajectories)
 T = dict(DIM=27, RHO_WIDTH=1458, SE_WIDTH=729, EXACT=0, LADDER_MAX=40, REC_WIDTH=64, REC_NJUMPS=54,
          REC_JUMP0=55, REC_JUMPS=4, REC_ITERS=63)
@@ -68,7 +74,7 @@ EXPORTED = ("ryd_abi_version", "ryd_last_error", "ryd_param_count", "ryd_summary
             "ryd_run_trajectories", "ryd_run_trajectories_device",
             "ryd_mixed_phase", "ryd_lapack_pool", "ryd_last_timeline", "ryd_mark", "ryd_mark_elapsed",
             "ryd_malloc", "ryd_free", "ryd_memcpy_h2d", "ryd_memcpy_d2h", "ryd_synchronize", "ryd_evolve_generic",
-            "ryd_derive", "ryd_derive_device")
+            "ryd_derive", "ryd_derive_device", "ryd_run_schedule", "ryd_run_schedule_device")
 
 # device derivation (ryd_derive): input fields, species-table columns, flags, diagnostic columns
 DV = dict(SPECIES=0, N_RYD=1, P1=2, P2=3, W1=4, W2=5, DELTA_E=6, LW1=7, LW2=8, TW_POWER=9, TW_WAIST=10,
@@ -102,6 +108,11 @@ class BatchDesc(ctypes.Structure):
                 ("n_steps", ctypes.c_int32), ("flags", ctypes.c_uint32),
                 ("rtol", ctypes.c_double), ("atol", ctypes.c_double),
                 ("max_steps", ctypes.c_int64)]
+
+
+class SchedDesc(ctypes.Structure):
+    _fields_ = [("abi_version", ctypes.c_int32), ("dim", ctypes.c_int32),
+                ("n_seg", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
 class TrajDesc(ctypes.Structure):
@@ -166,6 +177,11 @@ def load() -> ctypes.CDLL:
                                       ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(Stats)]
         lib.ryd_run_batch_device.argtypes = [vp, ctypes.c_int, ctypes.POINTER(BatchDesc), vp, i64, i64,
                                              vp, i64, vp, i64, vp, vp, ctypes.POINTER(ctypes.c_float)]
+        # (params, n, ld) then (sched, ld_sched), then the outputs of ryd_run_batch
+        lib.ryd_run_schedule.argtypes = [vp, ctypes.POINTER(SchedDesc), dp, i64, i64, dp, i64, dp, i64, dp, i64,
+                                         ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(Stats)]
+        lib.ryd_run_schedule_device.argtypes = [vp, ctypes.c_int, ctypes.POINTER(SchedDesc), vp, i64, i64, vp, i64,
+                                                vp, i64, vp, i64, vp, vp, ctypes.POINTER(ctypes.c_float)]
         lib.ryd_run_coherences.argtypes = [vp, ctypes.POINTER(BatchDesc), dp, i64, i64, dp, i64,
                                            ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(Stats)]
         lib.ryd_run_coherences_device.argtypes = [vp, ctypes.c_int, ctypes.POINTER(BatchDesc), vp, i64,

@@ -8,7 +8,7 @@ AtomicConfiguration :640), so callers can switch imports unchanged.
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import List, Optional, Tuple
+from typing import Any, List, Optional, Tuple
 
 import numpy as np
 
@@ -112,6 +112,38 @@ class SmoothJPSimulationInputs:
     @property
     def pulse_shape(self) -> str:
         return "smooth_sinusoidal"
+
+    @property
+    def n_pulses(self) -> int:
+        return 1
+
+
+@dataclass
+class PulseScheduleInputs:
+    """The caller's own pulse: piecewise-constant segments in units of each point's derived
+    two-photon Rabi frequency Omega (``pulse_schedules``).  ``x`` (Omega dt >= 0), ``amp``
+    (Omega_s / Omega >= 0), ``phase`` (radians) and ``delta`` (Delta_s / Omega) have shape
+    ``(n_seg,)`` -- one pulse for every point -- or ``(n, n_seg)``; scalars broadcast."""
+    excitation: TwoPhotonExcitationConfig = field(default_factory=TwoPhotonExcitationConfig)
+    noise: NoiseSourceConfig = field(default_factory=NoiseSourceConfig)
+    x: Any = None
+    amp: Any = 1.0
+    phase: Any = 0.0
+    delta: Any = 0.0
+
+    @classmethod
+    def from_table(cls, sched, **kw) -> "PulseScheduleInputs":
+        """From a ``pulse_schedules`` table of shape (4, n_seg) or (n, 4, n_seg)."""
+        s = np.asarray(sched, dtype=float)
+        return cls(x=s[..., 0, :], amp=s[..., 1, :], phase=s[..., 2, :], delta=s[..., 3, :], **kw)
+
+    @property
+    def protocol_name(self) -> str:
+        return "pulse_schedule"
+
+    @property
+    def pulse_shape(self) -> str:
+        return "schedule"
 
     @property
     def n_pulses(self) -> int:

@@ -1728,6 +1728,8 @@ __global__ __launch_bounds__(BLOCK, OCC) void jp_frame_kernel(
 #define RYD_LP_UNSQUARED 2                   // LP square, identical atoms: squaring levels left to the states
 #endif
 #include "ryd_sym16.inc"
+// custom pulse schedules on the same row layout (ryd_run_schedule)
+#include "ryd_sched16.inc"
 
 // ---------------------------------------------------------------------------
 // Adaptive Dormand-Prince 5(4) kernel (RYD_METHOD_DOPRI5)
@@ -2585,6 +2587,43 @@ int launch(const ryd_batch_desc* d, const double* dp, int64_t n, int64_t ldp, do
   return RYD_OK;
 }
 
+// ryd_run_schedule[_device]: the descriptor, the table pointer and the leading dimensions, all
+// before any GPU call.  has_state = false: a summary-only call, whose ld_state is ignored.
+int validate_schedule(const ryd_sched_desc* d, const double* sched, int64_t n, int64_t ldp, int64_t ldsc,
+                      int64_t lds, int64_t ldm, bool has_state) {
+  if (!d) return fail(RYD_ERR_INVALID, "desc is NULL");
+  if (!sched) return fail(RYD_ERR_INVALID, "schedule table is NULL");
+  if (d->abi_version != RYD_ABI_VERSION) return fail(RYD_ERR_INVALID, "abi_version mismatch");
+  if (d->n_seg < 1 || d->n_seg > RYD_SCHED_MAX_SEG)
+    return fail(RYD_ERR_INVALID, "n_seg must be 1 .. " + std::to_string(RYD_SCHED_MAX_SEG));
+  if (d->flags & ~(RYD_FLAG_SYMMETRIC_ATOMS | RYD_SCHED_SHARED)) return fail(RYD_ERR_INVALID, "unknown flag bits");
+  if (d->dim != 3) return fail(RYD_ERR_UNSUPPORTED, "pulse schedules run hilbert_space_dim 3 only");
+  if (!(d->flags & RYD_FLAG_SYMMETRIC_ATOMS))
+    return fail(RYD_ERR_UNSUPPORTED, "pulse schedules need identical atoms (RYD_FLAG_SYMMETRIC_ATOMS)");
+  if (!(d->flags & RYD_SCHED_SHARED) && ldsc < (int64_t)RYD_SC_NFIELD * d->n_seg)
+    return fail(RYD_ERR_INVALID, "ld_sched is smaller than 4 n_seg");
+  if (n < 0) return fail(RYD_ERR_INVALID, "n < 0");
+  if (ldp < n || (has_state && lds < 4 * n) || ldm < n) return fail(RYD_ERR_INVALID, "leading dimension too small");
+  return RYD_OK;
+}
+
+// One schedule batch on `stream` (ryd_sched16.inc); ds = NULL takes the store-free twin.  The
+// kernel addresses a shared table as a per-point one of leading dimension 0.
+int launch_schedule(const ryd_sched_desc* d, const double* dp, int64_t n, int64_t ldp, const double* dsc,
+                    int64_t ldsc, double* ds, int64_t lds, double* dm, int64_t ldm, uint32_t* dstat,
+                    hipStream_t stream) {
+  if (n == 0) return RYD_OK;
+  if (!ds) lds = 0;
+  // the output stores' 32-bit lane offsets, as launch_sym16 checks them
+  const int st32 = sym16_store32_enabled() && lds >= 0 && ldm >= 0 && lds <= (0x1fffffffLL - 15) / 3 &&
+                   ldm <= (0x1fffffffLL - 3) / 15;
+  const int64_t ld = (d->flags & RYD_SCHED_SHARED) ? 0 : ldsc;
+  const int nseg = d->n_seg;
+  return launch_typed(ds ? lindblad_sched16_kernel<true> : lindblad_sched16_kernel<false>,
+                      (n + S16_PPW - 1) / S16_PPW, S16_BLOCK, 0, stream, dp, n, ldp, dsc, ld, nseg, ds, lds, dm, ldm,
+                      dstat, st32);
+}
+
 // RYD_COH_PROP=0 selects coherence_cheb_kernel for every protocol (A/B and cross-check runs)
 bool coh_prop_enabled() { return !is_off(getenv("RYD_COH_PROP")); }
 
@@ -2689,6 +2728,18 @@ struct HostOut {
   int64_t ld;
   int rows;
   int per_point;
+};
+
+// A second per-point input of a partitioned run (the schedule table of ryd_run_schedule):
+// `row` doubles per point at host + i ld, or one shared row.  A slot's rows are one contiguous
+// block of the caller's table (the shared row: the row itself), staged and copied like the
+// parameter columns; run_partitioned sets `dev` to the slot's copy before it calls launch_fn.
+struct HostIn {
+  const double* host;
+  int64_t ld, row;
+  bool shared;
+  const double* dev = nullptr;
+  size_t count(int64_t cnt) const { return (size_t)(shared ? row : (cnt - 1) * ld + row); }
 };
 
 // Host worker threads for staging copies: RYD_HOST_THREADS, else min(16, cores).
@@ -2848,7 +2899,7 @@ void release_slot_work(ryd_slot_work& w) {
 template <typename LaunchFn>
 int run_partitioned(ryd_handle* h, const double* params, int64_t n, int64_t ld_params,
                     const std::vector<HostOut>& outs, uint32_t* out_status, LaunchFn launch_fn,
-                    double& kms, double& hms, double& dms) {
+                    double& kms, double& hms, double& dms, HostIn* extra = nullptr) {
   std::lock_guard<std::mutex> lock(h->mu);
   const auto t_call = std::chrono::steady_clock::now();
   const int nd = (int)h->dev.size();
@@ -2856,7 +2907,7 @@ int run_partitioned(ryd_handle* h, const double* params, int64_t n, int64_t ld_p
   if ((int)h->work.size() < nd) h->work.resize(nd);
   struct Part {
     int64_t off, cnt;
-    size_t o_par, o_st;
+    size_t o_par, o_st, o_in = 0;
     std::vector<size_t> o_out;
     bool queued;
     double t_enq = 0.0, t_wait = 0.0;    // host ms since the call began: kernel enqueued, wait began
@@ -2890,6 +2941,10 @@ int run_partitioned(ryd_handle* h, const double* params, int64_t n, int64_t ld_p
     }
     P.o_st = at;
     at = align256(at + sizeof(uint32_t) * P.cnt);
+    if (extra) {
+      P.o_in = at;
+      at = align256(at + sizeof(double) * extra->count(P.cnt));
+    }
     hipError_t e = hipSetDevice(h->dev[k]);
     if (e != hipSuccess) return fail(RYD_ERR_HIP, std::string("set device: ") + hipGetErrorString(e));
     int rc = ensure_slot_work(h, k, at);
@@ -2905,6 +2960,9 @@ int run_partitioned(ryd_handle* h, const double* params, int64_t n, int64_t ld_p
       for (int c = 0; c < RYD_NPARAM; ++c)
         pack.push_back({hb + P.o_par + sizeof(double) * c * P.cnt, params + (int64_t)c * ld_params + P.off,
                         sizeof(double) * P.cnt});
+      if (extra)
+        pack.push_back({hb + P.o_in, extra->host + (extra->shared ? 0 : P.off * extra->ld),
+                        sizeof(double) * extra->count(P.cnt)});
     }
     parallel_copy(pack);
     pack_ms = host_ms_since(t0);
@@ -2927,6 +2985,10 @@ int run_partitioned(ryd_handle* h, const double* params, int64_t n, int64_t ld_p
     if (e == hipSuccess)
       e = hipMemcpyAsync(db + P.o_par, hb + P.o_par, sizeof(double) * RYD_NPARAM * P.cnt,
                          hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && extra) {
+      e = hipMemcpyAsync(db + P.o_in, hb + P.o_in, sizeof(double) * extra->count(P.cnt), hipMemcpyHostToDevice, s);
+      extra->dev = (const double*)(db + P.o_in);
+    }
     if (e == hipSuccess) e = hipEventRecord(W.ev[1], s);
     if (e != hipSuccess) {
       drain(k);
@@ -3219,6 +3281,46 @@ int ryd_run_batch(ryd_handle* h, const ryd_batch_desc* desc, const double* param
         return launch(desc, dp, cnt, ldp, out_state ? o[0] : nullptr, 4 * cnt, o.back(), cnt, dst, s);
       },
       kms, hms, dms);
+  if (rc) return rc;
+  fill_stats(stats, h, kms, hms, dms, out_summary, ld_summary, n, RYD_S_NMV_USEFUL, RYD_S_NMV_EXEC);
+  return RYD_OK;
+}
+
+int ryd_run_schedule_device(ryd_handle* h, int slot, const ryd_sched_desc* desc, const double* d_params,
+                            int64_t n, int64_t ld_params, const double* d_sched, int64_t ld_sched,
+                            double* d_state, int64_t ld_state, double* d_summary, int64_t ld_summary,
+                            uint32_t* d_status, void* stream, float* elapsed_ms) {
+  return on_slot(
+      h, slot, stream, elapsed_ms,
+      [&] { return validate_schedule(desc, d_sched, n, ld_params, ld_sched, ld_state, ld_summary, d_state != nullptr); },
+      [&](hipStream_t s) {
+        return launch_schedule(desc, d_params, n, ld_params, d_sched, ld_sched, d_state, ld_state, d_summary,
+                               ld_summary, d_status, s);
+      });
+}
+
+int ryd_run_schedule(ryd_handle* h, const ryd_sched_desc* desc, const double* params, int64_t n,
+                     int64_t ld_params, const double* sched, int64_t ld_sched, double* out_state,
+                     int64_t ld_state, double* out_summary, int64_t ld_summary, uint32_t* out_status,
+                     ryd_stats* stats) {
+  // the descriptor first, so that each refusal reports its own reason with or without a handle
+  int rc = validate_schedule(desc, sched, n, ld_params, ld_sched, ld_state, ld_summary, out_state != nullptr);
+  if (rc) return rc;
+  if (!h) return fail(RYD_ERR_INVALID, "handle is NULL");
+  if (n > 0 && (!params || !out_summary || !out_status)) return fail(RYD_ERR_INVALID, "NULL buffer");
+  std::vector<HostOut> outs;
+  if (out_state) outs.push_back({out_state, ld_state, NC, 4});
+  outs.push_back({out_summary, ld_summary, RYD_NSUMMARY, 1});
+  HostIn tab = {sched, ld_sched, (int64_t)RYD_SC_NFIELD * desc->n_seg, (desc->flags & RYD_SCHED_SHARED) != 0};
+  double kms, hms, dms;
+  rc = run_partitioned(
+      h, params, n, ld_params, outs, out_status,
+      [&](const double* dp, int64_t cnt, int64_t ldp, int64_t, const std::vector<double*>& o, uint32_t* dst,
+          hipStream_t s) {
+        return launch_schedule(desc, dp, cnt, ldp, tab.dev, ld_sched, out_state ? o[0] : nullptr, 4 * cnt, o.back(),
+                               cnt, dst, s);
+      },
+      kms, hms, dms, &tab);
   if (rc) return rc;
   fill_stats(stats, h, kms, hms, dms, out_summary, ld_summary, n, RYD_S_NMV_USEFUL, RYD_S_NMV_EXEC);
   return RYD_OK;

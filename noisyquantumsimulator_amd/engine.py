@@ -135,6 +135,8 @@ def protocol_key(batch: DerivedBatch) -> str:
         return "lp_shaped"
     if batch.protocol == "smooth_jp":
         return "smooth_jp"
+    if batch.protocol == "pulse_schedule":
+        return "schedule"                    # Engine.run_schedule: not a protocol of Engine.run
     return "bangbang"
 
 
@@ -170,6 +172,8 @@ def pack_params(batch: DerivedBatch, idx: Optional[np.ndarray] = None) -> np.nda
         p[P["A"]] = c["A"][sel]
         p[P["OMEGA_MOD"]] = c["omega_mod"][sel]
         p[P["PHI_OFF"]] = c["phi_offset"][sel]
+    elif key == "schedule":
+        pass                                 # the table carries the pulse; the protocol columns stay 0
     else:
         t = batch.bangbang_times[sel]
         ph = batch.bangbang_phases[sel]
@@ -213,6 +217,26 @@ def symmetric_atoms(params: np.ndarray) -> bool:
     P = N.P
     return all(np.array_equal(params[P[k + "_A"]], params[P[k + "_B"]])
                for k in ("G1", "G0", "GPHI", "GSC", "GMJ"))
+
+
+def schedule_desc(params: np.ndarray, sched: np.ndarray) -> Tuple[N.SchedDesc, np.ndarray, int]:
+    """(descriptor, contiguous table, ld_sched) of a schedule run on ``params`` (NPARAM, n):
+    the table is checked (``pulse_schedules.validate_schedule``) except for its values, which
+    the kernel checks per point (status BAD_INPUT), and unequal atoms are refused."""
+    n = params.shape[1]
+    tab = np.ascontiguousarray(sched, dtype=np.float64)
+    if tab.ndim not in (2, 3) or tab.shape[-2] != N.SC_NFIELD or (tab.ndim == 3 and tab.shape[0] != n):
+        raise ValueError(f"sched must have shape ({n}, 4, n_seg) or (4, n_seg), not {tab.shape}")
+    if not 1 <= tab.shape[-1] <= N.SCHED_MAX_SEG:
+        raise ValueError(f"a schedule has 1 .. {N.SCHED_MAX_SEG} segments, not {tab.shape[-1]}")
+    if not symmetric_atoms(params):
+        raise ValueError("pulse schedules run identical atoms only: the atom-A and atom-B rate columns differ")
+    d = N.SchedDesc()
+    d.abi_version = N.RYD_ABI_VERSION
+    d.dim = 3
+    d.n_seg = tab.shape[-1]
+    d.flags = N.FLAG_SYMMETRIC_ATOMS | (N.RYD_SCHED_SHARED if tab.ndim == 2 else 0)
+    return d, tab, N.SC_NFIELD * tab.shape[-1]
 
 
 def check_coherence_dim(params: np.ndarray, dim: int) -> None:
@@ -322,6 +346,29 @@ class Engine:
             status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(st)))
         return EngineResult(evolution, n, state, summ, status, st.kernel_ms, st.h2d_ms, st.d2h_ms,
                             st.matvec_useful, st.matvec_exec, dim)
+
+    def run_schedule(self, params: np.ndarray, sched: np.ndarray, *, states: bool = True) -> EngineResult:
+        """The caller's own pulse (ryd_run_schedule): ``sched`` is a table of piecewise-constant
+        segments, shape ``(n, 4, n_seg)`` per point or ``(4, n_seg)`` shared by every point
+        (``pulse_schedules``; fields ``_native.SC``).  Lindblad, dim 3, identical atoms: unequal
+        atom-A / atom-B rate columns are refused.  The result is that of ``run(...,
+        "lindblad")``; ``states=False`` is a summary-only run."""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        if params.shape[0] != N.NPARAM:
+            raise ValueError(f"params must have shape ({N.NPARAM}, n)")
+        n = params.shape[1]
+        desc, tab, ld = schedule_desc(params, sched)
+        state = np.empty((N.STATE_WIDTH["lindblad"], 4 * n), dtype=np.float64) if states else None
+        summ = np.empty((N.NSUMMARY, n), dtype=np.float64)
+        status = np.zeros(n, dtype=np.uint32)
+        st = N.Stats()
+        dptr = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        N.check(self.lib.ryd_run_schedule(
+            self.handle, ctypes.byref(desc), dptr(params), n, n, dptr(tab), ld,
+            dptr(state) if states else None, 4 * n, dptr(summ), n,
+            status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(st)))
+        return EngineResult("lindblad", n, state, summ, status, st.kernel_ms, st.h2d_ms, st.d2h_ms,
+                            st.matvec_useful, st.matvec_exec, 3)
 
     def last_timeline(self) -> Dict[str, Any]:
         """ryd_last_timeline: host staging times and the per-slot HIP-event timeline of the
@@ -470,6 +517,67 @@ class DeviceBatch:
         N.check(lib.ryd_memcpy_d2h(h, s, status.ctypes.data, self.d_status, status.nbytes))
         return EngineResult(self.evolution, self.n, state, summ, status, 0.0, 0.0, 0.0,
                             summ[N.S["NMV_USEFUL"]].sum(), summ[N.S["NMV_EXEC"]].sum(), self.dim)
+
+    def free(self):
+        for p in self._bufs:
+            self.eng.lib.ryd_free(self.eng.handle, self.slot, p)
+        self._bufs = []
+
+
+class ScheduleDeviceBatch:
+    """A schedule run (ryd_run_schedule_device) with parameters and table resident in HBM on
+    one device slot, for timed re-runs; ``sched`` as ``Engine.run_schedule`` takes it."""
+
+    def __init__(self, engine: Engine, params: np.ndarray, sched: np.ndarray, slot: int = 0,
+                 states: bool = True):
+        self.eng, self.slot = engine, slot
+        self.states = states                 # False: summary-only, no d_state (NULL is passed)
+        lib = engine.lib
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        if params.shape[0] != N.NPARAM:
+            raise ValueError(f"params must have shape ({N.NPARAM}, n)")
+        self.n = n = params.shape[1]
+        self.desc, tab, self.ld_sched = schedule_desc(params, sched)
+        self.width = N.STATE_WIDTH["lindblad"]
+        self._bufs = []
+
+        def alloc(nbytes):
+            p = ctypes.c_void_p()
+            N.check(lib.ryd_malloc(engine.handle, slot, max(nbytes, 16), ctypes.byref(p)))
+            self._bufs.append(p)
+            return p
+        self.d_params = alloc(params.nbytes)
+        self.d_sched = alloc(tab.nbytes)
+        self.d_state = alloc(8 * self.width * 4 * n) if states else None
+        self.d_summary = alloc(8 * N.NSUMMARY * n)
+        self.d_status = alloc(4 * n)
+        N.check(lib.ryd_memcpy_h2d(engine.handle, slot, self.d_params, params.ctypes.data, params.nbytes))
+        N.check(lib.ryd_memcpy_h2d(engine.handle, slot, self.d_sched, tab.ctypes.data, tab.nbytes))
+
+    def launch(self, timed: bool = False) -> float:
+        """Enqueue one propagation of the whole batch; with ``timed`` wait and return the
+        kernel's device time (HIP events on the launch stream)."""
+        ms = ctypes.c_float(0.0)
+        N.check(self.eng.lib.ryd_run_schedule_device(
+            self.eng.handle, self.slot, ctypes.byref(self.desc), self.d_params, self.n, self.n,
+            self.d_sched, self.ld_sched, self.d_state, 4 * self.n, self.d_summary, self.n, self.d_status, None,
+            ctypes.byref(ms) if timed else None))
+        return float(ms.value)
+
+    def synchronize(self):
+        N.check(self.eng.lib.ryd_synchronize(self.eng.handle))
+
+    def fetch(self) -> EngineResult:
+        lib, h, s = self.eng.lib, self.eng.handle, self.slot
+        state = np.zeros((self.width, 4 * self.n)) if self.states else None
+        summ = np.zeros((N.NSUMMARY, self.n))
+        status = np.zeros(self.n, dtype=np.uint32)
+        if self.states:
+            N.check(lib.ryd_memcpy_d2h(h, s, state.ctypes.data, self.d_state, state.nbytes))
+        N.check(lib.ryd_memcpy_d2h(h, s, summ.ctypes.data, self.d_summary, summ.nbytes))
+        N.check(lib.ryd_memcpy_d2h(h, s, status.ctypes.data, self.d_status, status.nbytes))
+        return EngineResult("lindblad", self.n, state, summ, status, 0.0, 0.0, 0.0,
+                            summ[N.S["NMV_USEFUL"]].sum(), summ[N.S["NMV_EXEC"]].sum(), 3)
 
     def free(self):
         for p in self._bufs:

@@ -151,6 +151,7 @@ class DerivedBatch:
     cols: Dict[str, np.ndarray] = field(default_factory=dict)
     bangbang_times: Optional[np.ndarray] = None     # (n, nseg-1) dimensionless
     bangbang_phases: Optional[np.ndarray] = None    # (n, nseg)
+    schedule: Optional[np.ndarray] = None           # pulse_schedule: (4, n_seg) shared or (n, 4, n_seg)
     warnings: list = field(default_factory=list)
     noise_config: Any = None                        # the NoiseSourceConfig the points share
     status_bits: Optional[np.ndarray] = None        # (n,) RYD_STATUS_* warning bits per point
@@ -239,6 +240,8 @@ def concat_batches(parts: List["DerivedBatch"]) -> "DerivedBatch":
                         cols={k: np.concatenate([b.cols[k] for b in parts]) for k in b0.cols},
                         bangbang_times=cat([b.bangbang_times for b in parts]),
                         bangbang_phases=cat([b.bangbang_phases for b in parts]),
+                        schedule=(b0.schedule if b0.schedule is None or b0.schedule.ndim == 2
+                                  else cat([b.schedule for b in parts])),
                         warnings=flags, noise_config=b0.noise_config,
                         status_bits=cat([b.status_bits for b in parts]))
 
@@ -261,11 +264,20 @@ def derive_batch(simulation_inputs, n: Optional[int] = None, *, species="Rb87",
     simulation_inputs object per point.
     """
     from .configurations import (JPSimulationInputs, LPSimulationInputs,
-                                 SmoothJPSimulationInputs)
+                                 PulseScheduleInputs, SmoothJPSimulationInputs)
     ov = dict(overrides or {})
     si = simulation_inputs
+    sched = None
     if isinstance(si, LPSimulationInputs):
         protocol, pulse_shape = "levine_pichler", si.pulse_shape
+    elif isinstance(si, PulseScheduleInputs):
+        # the caller's own pulse: "schedule" takes the leakage spectral factor's "other" branch,
+        # as bang-bang and smooth JP do
+        from . import pulse_schedules as PS
+        protocol, pulse_shape = "pulse_schedule", "schedule"
+        if si.x is None:
+            raise ValueError("PulseScheduleInputs.x (the segment durations Omega dt) is required")
+        sched = PS.validate_schedule(PS.assemble(si.x, si.amp, si.phase, si.delta))
     elif isinstance(si, SmoothJPSimulationInputs):
         protocol, pulse_shape = "smooth_jp", "smooth_sinusoidal"
     elif isinstance(si, JPSimulationInputs):
@@ -281,6 +293,12 @@ def derive_batch(simulation_inputs, n: Optional[int] = None, *, species="Rb87",
                        tweezer_waist=tweezer_waist, tweezer_wavelength_nm=tweezer_wavelength_nm,
                        temperature=temperature, B_field=B_field, NA=NA, spacing_factor=spacing_factor,
                        overrides=ov)
+        if sched is not None and sched.ndim == 3:
+            if n not in (1, sched.shape[0]):
+                raise ValueError(f"a per-point schedule for {sched.shape[0]} points in a batch of {n}")
+            n = sched.shape[0]
+    if sched is not None and sched.ndim == 3 and sched.shape[0] != n:
+        raise ValueError(f"a per-point schedule for {sched.shape[0]} points in a batch of {n}")
     exc, noise = si.excitation, si.noise
     L1, L2 = exc.laser_1, exc.laser_2
     P1 = _bc(ov.get("laser_1_power", L1.power), n)
@@ -351,6 +369,14 @@ def derive_batch(simulation_inputs, n: Optional[int] = None, *, species="Rb87",
         elif protocol == "jandura_pupillo":
             otv = ov.get("omega_tau", si.omega_tau)
             ot = _bc(otv if otv is not None else P.JP_BANGBANG_OMEGA_TAU, m.sum())
+            tau_s = ot / Om
+            tau_t = tau_s
+            Dg = np.zeros(m.sum())
+            dom = np.zeros(m.sum())
+        elif protocol == "pulse_schedule":
+            # the pulse area is the table's: tau_total = sum_s x_s / Omega
+            xs = sched[..., 0, :].sum(axis=-1)
+            ot = _bc(xs[m] if np.ndim(xs) else xs, m.sum())
             tau_s = ot / Om
             tau_t = tau_s
             Dg = np.zeros(m.sum())
@@ -532,7 +558,7 @@ def derive_batch(simulation_inputs, n: Optional[int] = None, *, species="Rb87",
             cols["combined_polarization_purity"] = np.full(n, pur)
     return DerivedBatch(protocol=protocol, pulse_shape=pulse_shape, dim=hilbert_space_dim,
                         include_noise=include_noise, trap_laser_on=trap_laser_on, n=n, cols=cols,
-                        bangbang_times=bb_t, bangbang_phases=bb_p, warnings=flags,
+                        bangbang_times=bb_t, bangbang_phases=bb_p, schedule=sched, warnings=flags,
                         noise_config=noise, status_bits=bits)
 
 

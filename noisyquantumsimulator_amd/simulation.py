@@ -458,6 +458,16 @@ def simulate_CZ_gate_batch(simulation_inputs, n: Optional[int] = None, *, specie
     D = dim * dim
     from concurrent.futures import ThreadPoolExecutor
     from . import engine as E
+    from .configurations import PulseScheduleInputs
+    is_sched = isinstance(simulation_inputs, PulseScheduleInputs)
+    if is_sched:
+        # the schedule kernel is the dim-3 Lindblad one; the process map needs the six qubit
+        # coherences, and no coherence kernel reads a schedule table
+        if process_fidelity:
+            raise ValueError("process_fidelity=True is not available for PulseScheduleInputs: the coherence "
+                             "path (ryd_run_coherences) runs the built-in protocols only")
+        if dim != 3:
+            raise ValueError("PulseScheduleInputs runs hilbert_space_dim=3 only")
     t_start = time.perf_counter()
     dkw = dict(species=species, n_rydberg=n_rydberg, qubit_0=qubit_0, qubit_1=qubit_1,
                hilbert_space_dim=hilbert_space_dim, tweezer_power=tweezer_power,
@@ -467,6 +477,8 @@ def simulate_CZ_gate_batch(simulation_inputs, n: Optional[int] = None, *, specie
                trap_laser_on=trap_laser_on, overrides=overrides)
     nn = n if n is not None else PH.batch_size(**{k: v for k, v in dkw.items()
                                                    if k in PH.POINT_ARGS or k == "overrides"})
+    if is_sched and n is None and np.ndim(simulation_inputs.x) == 2:
+        nn = max(nn, np.shape(simulation_inputs.x)[0]) if nn > 1 else np.shape(simulation_inputs.x)[0]
     host_eigh = phase_penalty == "reference" and eigh not in (None, "scipy")
     native_epilogue = phase_penalty == "reference" and not host_eigh
     # chunks: derivation and the GPU pass of chunk k + 1 run on this thread while the host
@@ -474,7 +486,7 @@ def simulate_CZ_gate_batch(simulation_inputs, n: Optional[int] = None, *, specie
     # chunk order; each rho's zheevr calls are the same as in one call, so the phases and
     # flags are too).  The derivation is elementwise, so the chunks' columns are the
     # whole call's (tests/test_pipeline_cpu.py).
-    k = min(PIPELINE_CHUNKS, nn // PIPELINE_MIN_CHUNK) if native_epilogue else 1
+    k = min(PIPELINE_CHUNKS, nn // PIPELINE_MIN_CHUNK) if native_epilogue and not is_sched else 1
     bounds = [(0, nn)]
     if k > 1:
         # the first chunk is half the others: the epilogue pool starts sooner
@@ -516,6 +528,8 @@ def simulate_CZ_gate_batch(simulation_inputs, n: Optional[int] = None, *, specie
             # mesolve with an empty c_op list evolves kets (RG/simulation.py:683-690)
             ket_mask = (np.all([x == 0 for x in g], axis=0) & (b.mj_rate() == 0)) if include_noise \
                 else np.ones(b.n, bool)
+            if is_sched:                            # every schedule point is a Lindblad point (zero
+                ket_mask = np.zeros(b.n, bool)      # rates: a pure rho)
             ket_all[lo:hi] = ket_mask
             if b.status_bits is not None:
                 status[lo:hi] |= b.status_bits
@@ -526,8 +540,12 @@ def simulate_CZ_gate_batch(simulation_inputs, n: Optional[int] = None, *, specie
                 idx = lo + loc
                 t0 = time.perf_counter()
                 prm = E.pack_params(b, loc)
-                r = eng.run(prm, key, evol, shape=shape, method=method if dim == 3 else "chebyshev", dim=dim,
-                            states=needs_state(evol, phase_penalty, return_states, process_fidelity))
+                want = needs_state(evol, phase_penalty, return_states, process_fidelity)
+                if is_sched:
+                    r = eng.run_schedule(prm, b.schedule if b.schedule.ndim == 2 else b.schedule[loc], states=want)
+                else:
+                    r = eng.run(prm, key, evol, shape=shape, method=method if dim == 3 else "chebyshev", dim=dim,
+                                states=want)
                 coh = None
                 if process_fidelity and evol == "lindblad":
                     coh, cst = eng.run_coherences(prm, key, shape=shape, dim=dim)
@@ -611,7 +629,7 @@ def noise_breakdown_row(b: PH.DerivedBatch, i: int, n_collapse_ops: Optional[int
 
 def _protocol_name(protocol: str) -> str:
     return {"levine_pichler": "levine_pichler", "smooth_jp": "smooth_jp",
-            "jandura_pupillo": "jandura_pupillo"}[protocol]
+            "jandura_pupillo": "jandura_pupillo", "pulse_schedule": "pulse_schedule"}[protocol]
 
 
 def simulate_CZ_gate(
@@ -676,6 +694,13 @@ def simulate_CZ_gate(
                       "protocol_variant": "bluvstein_evered_dark_state", "A": c["A"],
                       "omega_mod_ratio": c["omega_mod"] / c["Omega"], "phi_offset": c["phi_offset"],
                       "delta_over_omega": c["smooth_delta_over_omega"]}
+        n_pulses = 1
+    elif protocol == "pulse_schedule":
+        tab = b.schedule if b.schedule.ndim == 2 else b.schedule[0]
+        pulse_info = {"shape": "schedule", "implementation": "piecewise_constant_hamiltonian",
+                      "protocol_variant": "custom_pulse_schedule", "n_segments": tab.shape[-1],
+                      "x": list(tab[0]), "amp": list(tab[1]), "phase": list(tab[2]), "delta": list(tab[3]),
+                      "omega_tau": c["omega_tau"]}
         n_pulses = 1
     else:
         pulse_info = {"shape": "bangbang", "implementation": "piecewise_constant_hamiltonian",

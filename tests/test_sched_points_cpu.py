@@ -1,0 +1,45 @@
+"""The oracle chains behind tests/test_gpu_schedule.py, recomputed here on the CPU: every
+batch's chain (tests/sched_points.py: evolve_state(method="expm") over the segments) is finite,
+trace-preserving to 1e-12 and Hermitian, so the inputs stay inside the oracle's own range, and
+it equals the recorded tests/golden/sched_oracle.npz the GPU tests read."""
+import numpy as np
+import pytest
+
+from noisyquantumsimulator_amd import _native as N
+from tests import sched_points as SP
+
+
+def test_batches_are_what_the_issue_asks():
+    b = SP.batch("random")
+    s = b["sched"]
+    assert b["params"].shape == (N.NPARAM, 13) and s.shape == (13, 4, 20)
+    assert np.all((s[:, N.SC["X"]] == 0).sum(axis=1) == 1) and np.all((s[:, N.SC["AMP"]] == 0).sum(axis=1) == 1)
+    assert np.all(np.abs(s[:, N.SC["PHASE"]]) <= np.pi) and np.all(np.abs(s[:, N.SC["DELTA"]]) < 0.5)
+    for name in ("lp_square", "bangbang", "smooth_jp"):
+        assert SP.batch(name)["params"].shape[1] == 9
+    assert SP.batch("smooth_jp")["sched"].shape == (9, 4, 300)
+    assert np.all((SP.batch("bangbang")["sched"][:, N.SC["X"]] == 0).sum(axis=1) == 1)
+    for ns in SP.CHUNK_NSEG:
+        c = SP.batch(f"chunk{ns}")["sched"]
+        assert c.shape == (5, 4, ns) and np.all(c[:, N.SC["AMP"]] == 1) and np.ptp(c[:, N.SC["X"]]) == 0
+    for name in SP.NAMES:
+        p = SP.batch(name)["params"]
+        for k in ("G1", "G0", "GPHI", "GSC"):
+            np.testing.assert_array_equal(p[N.P[k + "_A"]], p[N.P[k + "_B"]])
+        assert SP.golden(name).shape == (p.shape[1], 4, 9, 9)
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("name", SP.NAMES)
+def test_oracle_chain(name):
+    b = SP.batch(name)
+    rho = SP.oracle_chain(b["params"], b["sched"])
+    assert np.all(np.isfinite(rho))
+    tr = np.trace(rho, axis1=2, axis2=3)
+    herm = float(np.abs(rho - rho.conj().transpose(0, 1, 3, 2)).max())
+    drift = float(np.abs(rho - SP.golden(name)).max())
+    print(f"{name}: max|Tr rho - 1| = {np.abs(tr - 1).max():.2e}, non-Hermitian part {herm:.2e}, "
+          f"against the recorded chain {drift:.2e}")
+    assert np.abs(tr - 1).max() < 1e-12 and herm < 1e-12
+    # the recorded chain is this chain (another LAPACK build may round differently)
+    assert drift < 1e-12
