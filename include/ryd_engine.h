@@ -423,6 +423,31 @@ int ryd_run_coherences_device(ryd_handle* h, int slot, const ryd_batch_desc* des
                               double* d_coh, int64_t ld_coh, uint32_t* d_status,
                               void* stream, float* elapsed_ms);
 
+/* Process-map coherences of a custom pulse schedule: the rows of ryd_run_coherences (layout
+ * above, exactly) for the caller's table, which is passed as the schedule entry points above
+ * take it (descriptor, params, table, ld_sched, RYD_SCHED_SHARED).  With the four diagonal
+ * inputs of a schedule run on the same params and table they make the full qubit process map:
+ * both kernels take a segment's (cos, sin) from the same function, so states and coherences
+ * are carried in the same frame.  Lindblad, dim 3, identical atoms; one kernel,
+ * coherence_sched_kernel (csrc/ryd_coh_sched.inc), four points per wave, one propagator per
+ * sector per run of equal (a_s Omega, delta_s Omega, x_s / Omega), compared exactly.  Segment
+ * semantics as above: zero duration is skipped, a_s = 0 is free evolution.
+ * out_coh: RYD_NCOH rows, ld_coh >= n.  Status per point: RYD_STATUS_BAD_INPUT on exactly the
+ * points where the schedule run puts it, RYD_STATUS_STEP_CAP for a segment beyond the build's
+ * argument cap -- either way the point's rows hold the identity images E(|a><b|) = |a><b| --
+ * and RYD_STATUS_NONFINITE.  Refused before any GPU call, descriptor first, by the rules of
+ * the schedule entry points, plus ld_coh < n (RYD_ERR_INVALID).  RYD_COH_PROP does not apply. */
+int ryd_run_schedule_coherences(ryd_handle* h, const ryd_sched_desc* desc,
+                                const double* params, int64_t n, int64_t ld_params,
+                                const double* sched, int64_t ld_sched,
+                                double* out_coh, int64_t ld_coh,
+                                uint32_t* out_status, ryd_stats* stats);
+int ryd_run_schedule_coherences_device(ryd_handle* h, int slot, const ryd_sched_desc* desc,
+                                       const double* d_params, int64_t n, int64_t ld_params,
+                                       const double* d_sched, int64_t ld_sched,
+                                       double* d_coh, int64_t ld_coh, uint32_t* d_status,
+                                       void* stream, float* elapsed_ms);
+
 /* Three-atom quantum-jump trajectories (layout above).  Host-buffer form:
  * range-partitions the points over the handle's devices; rho and se are packed
  * (ld = RYD_T_RHO_WIDTH / RYD_T_SE_WIDTH); records may be NULL.  stats->

@@ -24,9 +24,9 @@ from .optimize_cz_gate import (JP_PHASES_DEFAULT, JP_SWITCHING_TIMES_DEFAULT, Ap
                                optimize_cz_gate, run_baseline)
 from .optimization import (EvaluatedPoint, ExplorationResult, HardwareOptimizationResult,
                            combine_explorations, explore_parameter_space, optimize_CZ_parameters)
-from .engine import Engine, DeviceBatch
+from .engine import Engine, DeviceBatch, ScheduleCoherenceDeviceBatch
 from . import pulse_schedules
-from .noise_models import gate_process_maps
+from .noise_models import gate_process_maps, schedule_process_maps
 from .calibration import calibrate_cz, load_calibration, write_calibration
 
 __all__ = [
@@ -49,5 +49,5 @@ __all__ = [
     # engine, process maps, calibration files (beyond the reference)
     "Engine", "DeviceBatch", "gate_process_maps", "calibrate_cz", "write_calibration", "load_calibration",
     # the caller's own pulse as a table of piecewise-constant segments (beyond the reference)
-    "PulseScheduleInputs", "pulse_schedules",
+    "PulseScheduleInputs", "pulse_schedules", "schedule_process_maps", "ScheduleCoherenceDeviceBatch",
 ]

@@ -117,8 +117,11 @@ def calibrate_cz(simulation_inputs, root: str, *, species="Rb87", n_rydberg=70, 
         b = br.batch
         key = E.protocol_key(b)
         shape = b.pulse_shape.lower() if key == "lp_shaped" else "square"
-        maps = NM.gate_process_maps(E.pack_params(b), key, shape=shape,
-                                    engine=E.Engine(list(devices)) if devices else None, dim=b.dim)
+        eng = E.Engine(list(devices)) if devices else None
+        if key == "schedule":                # the caller's own pulse: its table instead of a protocol
+            maps = NM.schedule_process_maps(E.pack_params(b), b.schedule, engine=eng)
+        else:
+            maps = NM.gate_process_maps(E.pack_params(b), key, shape=shape, engine=eng, dim=b.dim)
     full_app = {k: np.broadcast_to(np.asarray(apparatus.get(k, d), dtype=float), (n,))
                 for k, d in zip(APPARATUS_KEYS, (30e-3, 1.0e-6, 2e-6, 1e-4, 0.5, 2.8))}
     recs = records(br, full_app, maps)

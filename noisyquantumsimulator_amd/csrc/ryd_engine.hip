@@ -2212,6 +2212,8 @@ __global__ __launch_bounds__(BLOCK) void coherence_cheb_kernel(const double* __r
 #include "ryd_dim4_prop.inc"
 #include "ryd_coh4_prop.inc"
 #include "ryd_shaped16.inc"
+// process-map coherences of a custom pulse schedule (ryd_run_schedule_coherences)
+#include "ryd_coh_sched.inc"
 
 // ---------------------------------------------------------------------------
 // host side
@@ -2645,6 +2647,28 @@ int launch_coherences(const ryd_batch_desc* d, const double* dp, int64_t n, int6
     return launch_typed(dim4 ? coherence4_cheb_kernel<P> : coherence_cheb_kernel<P>, 2 * nb2 + 2 * nb1, BLOCK, 0,
                         stream, dp, n, ldp, dc, ldc, dstat, ns, sh, b0, b1, b2);
   });
+}
+
+// ryd_run_schedule_coherences[_device]: validate_schedule's rules (the descriptor first), with
+// the coherence rows' leading dimension in place of the state's and the summary's
+int validate_schedule_coherences(const ryd_sched_desc* d, const double* sched, int64_t n, int64_t ldp,
+                                 int64_t ldsc, int64_t ldc) {
+  if (int rc = validate_schedule(d, sched, n, ldp, ldsc, 0, n, false)) return rc;
+  if (ldc < n) return fail(RYD_ERR_INVALID, "leading dimension too small");
+  return RYD_OK;
+}
+
+// The coherence sectors of one schedule batch (ryd_coh_sched.inc, one launch); status is cleared
+// first, as launch_coherences does.  A shared table is a per-point one of leading dimension 0.
+int launch_schedule_coherences(const ryd_sched_desc* d, const double* dp, int64_t n, int64_t ldp,
+                               const double* dsc, int64_t ldsc, double* dc, int64_t ldc, uint32_t* dstat,
+                               hipStream_t stream) {
+  if (n == 0) return RYD_OK;
+  HIPCHK(hipMemsetAsync(dstat, 0, sizeof(uint32_t) * n, stream));
+  const int64_t ld = (d->flags & RYD_SCHED_SHARED) ? 0 : ldsc;
+  const int nseg = d->n_seg;
+  return launch_typed(coherence_sched_kernel, (n + CP_NR - 1) / CP_NR, CP_BLOCK, 0, stream, dp, n, ldp, dsc, ld,
+                      nseg, dc, ldc, dstat);
 }
 
 int validate_coherences(const ryd_batch_desc* d, int64_t n, int64_t ldp, int64_t ldc) {
@@ -3343,6 +3367,42 @@ int ryd_run_coherences(ryd_handle* h, const ryd_batch_desc* desc, const double* 
   if (rc) return rc;
   fill_stats(stats, h, kms, hms, dms, nullptr, 0, 0, 0, 0);
   return RYD_OK;
+}
+
+int ryd_run_schedule_coherences(ryd_handle* h, const ryd_sched_desc* desc, const double* params, int64_t n,
+                                int64_t ld_params, const double* sched, int64_t ld_sched, double* out_coh,
+                                int64_t ld_coh, uint32_t* out_status, ryd_stats* stats) {
+  // the descriptor first, so that each refusal reports its own reason with or without a handle
+  int rc = validate_schedule_coherences(desc, sched, n, ld_params, ld_sched, ld_coh);
+  if (rc) return rc;
+  if (!h) return fail(RYD_ERR_INVALID, "handle is NULL");
+  if (n > 0 && (!params || !out_coh || !out_status)) return fail(RYD_ERR_INVALID, "NULL buffer");
+  const std::vector<HostOut> outs = {{out_coh, ld_coh, RYD_NCOH, 1}};
+  HostIn tab = {sched, ld_sched, (int64_t)RYD_SC_NFIELD * desc->n_seg, (desc->flags & RYD_SCHED_SHARED) != 0};
+  double kms, hms, dms;
+  rc = run_partitioned(
+      h, params, n, ld_params, outs, out_status,
+      [&](const double* dp, int64_t cnt, int64_t ldp, int64_t, const std::vector<double*>& o, uint32_t* dst,
+          hipStream_t s) {
+        return launch_schedule_coherences(desc, dp, cnt, ldp, tab.dev, ld_sched, o[0], cnt, dst, s);
+      },
+      kms, hms, dms, &tab);
+  if (rc) return rc;
+  fill_stats(stats, h, kms, hms, dms, nullptr, 0, 0, 0, 0);
+  return RYD_OK;
+}
+
+int ryd_run_schedule_coherences_device(ryd_handle* h, int slot, const ryd_sched_desc* desc, const double* d_params,
+                                       int64_t n, int64_t ld_params, const double* d_sched, int64_t ld_sched,
+                                       double* d_coh, int64_t ld_coh, uint32_t* d_status, void* stream,
+                                       float* elapsed_ms) {
+  return on_slot(
+      h, slot, stream, elapsed_ms,
+      [&] { return validate_schedule_coherences(desc, d_sched, n, ld_params, ld_sched, ld_coh); },
+      [&](hipStream_t s) {
+        return launch_schedule_coherences(desc, d_params, n, ld_params, d_sched, ld_sched, d_coh, ld_coh, d_status,
+                                          s);
+      });
 }
 
 int ryd_run_trajectories(ryd_handle* h, const ryd_traj_desc* desc, const double* params, int64_t n,

@@ -248,6 +248,19 @@ def check_coherence_dim(params: np.ndarray, dim: int) -> None:
         raise ValueError("params carry mJ leakage rates (GMJ_A / GMJ_B) that dim=3 would ignore; pass dim=4")
 
 
+def schedule_coherence_inputs(params: np.ndarray,
+                              sched: np.ndarray) -> Tuple[np.ndarray, N.SchedDesc, np.ndarray, int]:
+    """(contiguous params, descriptor, contiguous table, ld_sched) of a schedule coherence run:
+    ``schedule_desc``'s checks (table form, segment count, identical atoms) and, as for every
+    dim-3 coherence run, nonzero GMJ columns refused rather than ignored."""
+    params = np.ascontiguousarray(params, dtype=np.float64)
+    if params.ndim != 2 or params.shape[0] != N.NPARAM:
+        raise ValueError(f"params must have shape ({N.NPARAM}, n)")
+    check_coherence_dim(params, 3)
+    desc, tab, ld = schedule_desc(params, sched)
+    return params, desc, tab, ld
+
+
 def sym16_balance_plan(n: int, cus: int = 256, gpc: int = 0) -> Dict[str, Any]:
     """The static plan of the sym16 LP-square kernel's CU-balanced launch form for ``n`` points
     on ``cus`` compute units (``gpc`` > 0 overrides the groups per workgroup): ``groups``,
@@ -405,6 +418,21 @@ class Engine:
             status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(st)))
         return coh, status
 
+    def run_schedule_coherences(self, params: np.ndarray, sched: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """The coherence rows of ``run_coherences`` for the caller's own pulse
+        (ryd_run_schedule_coherences): ``sched`` as ``run_schedule`` takes it.  With the states of
+        ``run_schedule`` on the same inputs they make the process map
+        (``noise_models.schedule_process_maps``).  Returns (coh (NCOH, n), status (n,))."""
+        params, desc, tab, ld = schedule_coherence_inputs(params, sched)
+        n = params.shape[1]
+        coh = np.zeros((N.NCOH, n), dtype=np.float64)
+        status = np.zeros(n, dtype=np.uint32)
+        st = N.Stats()
+        dptr = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        N.check(self.lib.ryd_run_schedule_coherences(
+            self.handle, ctypes.byref(desc), dptr(params), n, n, dptr(tab), ld, dptr(coh), n,
+            status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(st)))
+        return coh, status
 
     def derive(self, inp, diag: bool = False) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
         """Hot-path row a1 on the GPU (ryd_derive): ``physics.derive_inputs(...)`` ->
@@ -719,6 +747,64 @@ class CoherenceDeviceBatch:
         N.check(self.eng.lib.ryd_run_coherences_device(
             self.eng.handle, self.slot, ctypes.byref(self.desc), self.d_params, self.n, self.n,
             self.d_coh, self.n, self.d_status, None, ctypes.byref(ms) if timed else None))
+        return float(ms.value)
+
+    def mark(self, which: int):
+        N.check(self.eng.lib.ryd_mark(self.eng.handle, self.slot, which))
+
+    def mark_elapsed(self) -> float:
+        ms = ctypes.c_float(0.0)
+        N.check(self.eng.lib.ryd_mark_elapsed(self.eng.handle, self.slot, ctypes.byref(ms)))
+        return float(ms.value)
+
+    def synchronize(self):
+        N.check(self.eng.lib.ryd_synchronize(self.eng.handle))
+
+    def fetch(self) -> Tuple[np.ndarray, np.ndarray]:
+        lib, h, s = self.eng.lib, self.eng.handle, self.slot
+        coh = np.zeros((N.NCOH, self.n))
+        status = np.zeros(self.n, dtype=np.uint32)
+        N.check(lib.ryd_memcpy_d2h(h, s, coh.ctypes.data, self.d_coh, coh.nbytes))
+        N.check(lib.ryd_memcpy_d2h(h, s, status.ctypes.data, self.d_status, status.nbytes))
+        return coh, status
+
+    def free(self):
+        for p in self._bufs:
+            self.eng.lib.ryd_free(self.eng.handle, self.slot, p)
+        self._bufs = []
+
+
+class ScheduleCoherenceDeviceBatch:
+    """The coherence sectors of a schedule (ryd_run_schedule_coherences_device) with parameters
+    and table resident in HBM on one device slot, for timed re-runs: the interface of
+    ``CoherenceDeviceBatch``, ``sched`` as ``Engine.run_schedule_coherences`` takes it."""
+
+    def __init__(self, engine: Engine, params: np.ndarray, sched: np.ndarray, slot: int = 0):
+        self.eng, self.slot = engine, slot
+        lib = engine.lib
+        params, self.desc, tab, self.ld_sched = schedule_coherence_inputs(params, sched)
+        self.dim = 3
+        self.n = n = params.shape[1]
+        self._bufs = []
+
+        def alloc(nbytes):
+            p = ctypes.c_void_p()
+            N.check(lib.ryd_malloc(engine.handle, slot, max(nbytes, 16), ctypes.byref(p)))
+            self._bufs.append(p)
+            return p
+        self.d_params = alloc(params.nbytes)
+        self.d_sched = alloc(tab.nbytes)
+        self.d_coh = alloc(8 * N.NCOH * n)
+        self.d_status = alloc(4 * n)
+        N.check(lib.ryd_memcpy_h2d(engine.handle, slot, self.d_params, params.ctypes.data, params.nbytes))
+        N.check(lib.ryd_memcpy_h2d(engine.handle, slot, self.d_sched, tab.ctypes.data, tab.nbytes))
+
+    def launch(self, timed: bool = False) -> float:
+        ms = ctypes.c_float(0.0)
+        N.check(self.eng.lib.ryd_run_schedule_coherences_device(
+            self.eng.handle, self.slot, ctypes.byref(self.desc), self.d_params, self.n, self.n,
+            self.d_sched, self.ld_sched, self.d_coh, self.n, self.d_status, None,
+            ctypes.byref(ms) if timed else None))
         return float(ms.value)
 
     def mark(self, which: int):

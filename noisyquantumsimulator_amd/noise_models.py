@@ -201,3 +201,17 @@ def gate_process_maps(params: np.ndarray, protocol: str, n_steps: Optional[int] 
     coh, cst = eng.run_coherences(params, protocol, n_steps=n_steps, shape=shape, dim=dim)
     S = assemble_maps(diag.state, coh, dim)
     return analyse(S, diag.status | cst, with_kraus=with_kraus)
+
+
+def schedule_process_maps(params: np.ndarray, sched: np.ndarray, engine=None,
+                          with_kraus: bool = False) -> ProcessMaps:
+    """Process maps of a batch of packed points under the caller's own pulse: ``sched`` is the
+    table ``Engine.run_schedule`` takes, shape ``(n, 4, n_seg)`` or ``(4, n_seg)`` shared.  The
+    diagonal inputs come from ``run_schedule``, the coherences from ``run_schedule_coherences``
+    (Lindblad, dim 3, identical atoms); the two statuses are OR-ed."""
+    from . import engine as E
+    eng = engine if engine is not None else E.Engine()
+    diag = eng.run_schedule(params, sched)
+    coh, cst = eng.run_schedule_coherences(params, sched)
+    S = assemble_maps(diag.state, coh, 3)
+    return analyse(S, diag.status | cst, with_kraus=with_kraus)

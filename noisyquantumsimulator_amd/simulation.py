@@ -461,8 +461,10 @@ def simulate_CZ_gate_batch(simulation_inputs, n: Optional[int] = None, *, specie
     from .configurations import PulseScheduleInputs
     is_sched = isinstance(simulation_inputs, PulseScheduleInputs)
     if is_sched:
-        # the schedule kernel is the dim-3 Lindblad one; the process map needs the six qubit
-        # coherences, and no coherence kernel reads a schedule table
+        # the schedule kernel is the dim-3 Lindblad one.  The process map of a schedule (its six
+        # qubit coherences from ryd_run_schedule_coherences) lives in
+        # noise_models.schedule_process_maps and calibrate_cz(..., with_process_map=True); this
+        # entry point's own process_fidelity path still goes through ryd_run_coherences
         if process_fidelity:
             raise ValueError("process_fidelity=True is not available for PulseScheduleInputs: the coherence "
                              "path (ryd_run_coherences) runs the built-in protocols only")
