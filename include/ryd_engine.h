@@ -411,6 +411,40 @@ int ryd_run_schedule_device(ryd_handle* h, int slot, const ryd_sched_desc* desc,
                             double* d_summary, int64_t ld_summary,
                             uint32_t* d_status, void* stream, float* elapsed_ms);
 
+/* The same tables without noise, as kets, and the phase gradients of the two diagonal overlaps
+ * (csrc/ryd_ket_sched.inc: ket_sched_kernel, ket_sched_jac_kernel; four points per wave).
+ * Descriptor, params, table, ld_sched and RYD_SCHED_SHARED as above; the rate columns are
+ * checked as above and otherwise ignored.  State, summary and status are those of
+ * ryd_run_batch for RYD_EVOL_KET, dim 3: 18 ket rows (ld_state >= 4 n, out_state may be NULL:
+ * a summary-only run), every RYD_S_* column (RYD_S_NSQUARE: forward propagator builds,
+ * RYD_S_NMV_USEFUL: forward segments applied), RYD_STATUS_BAD_INPUT (the point keeps its basis
+ * kets), RYD_STATUS_STEP_CAP (a segment beyond the ket build's argument cap is skipped) and
+ * RYD_STATUS_NONFINITE.
+ * out_jac (may be NULL: the forward kernel alone), point-major like the table:
+ *     jac[i * ld_jac + c * n_seg + s] = d a / d phi_s,   ld_jac >= 4 * n_seg,
+ *     c = 0: Re d a01, 1: Im d a01, 2: Re d a11, 3: Im d a11,
+ * with a01 = <01|psi_01> (RYD_S_OV_RE0/IM0 + 1) and a11 = <11|psi_11> (+ 3).  A skipped segment
+ * (zero duration, step cap) and every segment of a BAD_INPUT point get exact zeros.  State,
+ * summary and status do not depend on whether the Jacobian is asked for.  Refused before any
+ * GPU call, descriptor first, by the rules above, plus ld_jac < 4 n_seg where out_jac is given
+ * (RYD_ERR_INVALID). */
+int ryd_run_schedule_kets(ryd_handle* h, const ryd_sched_desc* desc,
+                          const double* params, int64_t n, int64_t ld_params,
+                          const double* sched, int64_t ld_sched,
+                          double* out_state, int64_t ld_state,
+                          double* out_summary, int64_t ld_summary,
+                          double* out_jac, int64_t ld_jac,
+                          uint32_t* out_status, ryd_stats* stats);
+/* Device buffers on slot `slot` (d_jac: (n - 1) * ld_jac + 4 * n_seg doubles, or NULL);
+ * d_state may be NULL. */
+int ryd_run_schedule_kets_device(ryd_handle* h, int slot, const ryd_sched_desc* desc,
+                                 const double* d_params, int64_t n, int64_t ld_params,
+                                 const double* d_sched, int64_t ld_sched,
+                                 double* d_state, int64_t ld_state,
+                                 double* d_summary, int64_t ld_summary,
+                                 double* d_jac, int64_t ld_jac,
+                                 uint32_t* d_status, void* stream, float* elapsed_ms);
+
 /* Process-map coherences (layout above).  Chebyshev state-vector method; any
  * protocol, either evolution value (rates may be zero).  Host-buffer form
  * range-partitions like ryd_run_batch; status bits as ryd_run_batch. */

@@ -24,7 +24,7 @@ from .optimize_cz_gate import (JP_PHASES_DEFAULT, JP_SWITCHING_TIMES_DEFAULT, Ap
                                optimize_cz_gate, run_baseline)
 from .optimization import (EvaluatedPoint, ExplorationResult, HardwareOptimizationResult,
                            combine_explorations, explore_parameter_space, optimize_CZ_parameters)
-from .engine import Engine, DeviceBatch, ScheduleCoherenceDeviceBatch
+from .engine import Engine, DeviceBatch, ScheduleCoherenceDeviceBatch, ScheduleKetDeviceBatch
 from . import pulse_schedules
 from .noise_models import gate_process_maps, schedule_process_maps
 from .calibration import calibrate_cz, load_calibration, write_calibration
@@ -50,4 +50,5 @@ __all__ = [
     "Engine", "DeviceBatch", "gate_process_maps", "calibrate_cz", "write_calibration", "load_calibration",
     # the caller's own pulse as a table of piecewise-constant segments (beyond the reference)
     "PulseScheduleInputs", "pulse_schedules", "schedule_process_maps", "ScheduleCoherenceDeviceBatch",
+    "ScheduleKetDeviceBatch",
 ]

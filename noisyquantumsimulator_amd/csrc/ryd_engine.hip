@@ -1730,6 +1730,8 @@ __global__ __launch_bounds__(BLOCK, OCC) void jp_frame_kernel(
 #include "ryd_sym16.inc"
 // custom pulse schedules on the same row layout (ryd_run_schedule)
 #include "ryd_sched16.inc"
+// the same tables as kets, with the overlaps' phase gradients (ryd_run_schedule_kets)
+#include "ryd_ket_sched.inc"
 
 // ---------------------------------------------------------------------------
 // Adaptive Dormand-Prince 5(4) kernel (RYD_METHOD_DOPRI5)
@@ -2626,6 +2628,32 @@ int launch_schedule(const ryd_sched_desc* d, const double* dp, int64_t n, int64_
                       dstat, st32);
 }
 
+// ryd_run_schedule_kets[_device]: validate_schedule's rules (the descriptor first), then the
+// Jacobian's leading dimension where a Jacobian is asked for
+int validate_schedule_kets(const ryd_sched_desc* d, const double* sched, int64_t n, int64_t ldp, int64_t ldsc,
+                           int64_t lds, int64_t ldm, bool has_state, int64_t ldj, bool has_jac) {
+  if (int rc = validate_schedule(d, sched, n, ldp, ldsc, lds, ldm, has_state)) return rc;
+  if (has_jac && ldj < (int64_t)RYD_SC_NFIELD * d->n_seg) return fail(RYD_ERR_INVALID, "ld_jac is smaller than 4 n_seg");
+  return RYD_OK;
+}
+
+// One noise-free schedule batch as kets on `stream` (ryd_ket_sched.inc); ds = NULL takes the
+// store-free twin, dj = NULL the forward kernel alone.
+int launch_schedule_kets(const ryd_sched_desc* d, const double* dp, int64_t n, int64_t ldp, const double* dsc,
+                         int64_t ldsc, double* ds, int64_t lds, double* dm, int64_t ldm, double* dj, int64_t ldj,
+                         uint32_t* dstat, hipStream_t stream) {
+  if (n == 0) return RYD_OK;
+  if (!ds) lds = 0;
+  const int64_t ld = (d->flags & RYD_SCHED_SHARED) ? 0 : ldsc;
+  const int nseg = d->n_seg;
+  const int64_t grid = (n + S16_PPW - 1) / S16_PPW;
+  if (dj)
+    return launch_typed(ds ? ket_sched_jac_kernel<true> : ket_sched_jac_kernel<false>, grid, S16_BLOCK, 0, stream, dp,
+                        n, ldp, dsc, ld, nseg, ds, lds, dm, ldm, dj, ldj, dstat);
+  return launch_typed(ds ? ket_sched_kernel<true> : ket_sched_kernel<false>, grid, S16_BLOCK, 0, stream, dp, n, ldp,
+                      dsc, ld, nseg, ds, lds, dm, ldm, dstat);
+}
+
 // RYD_COH_PROP=0 selects coherence_cheb_kernel for every protocol (A/B and cross-check runs)
 bool coh_prop_enabled() { return !is_off(getenv("RYD_COH_PROP")); }
 
@@ -2747,11 +2775,14 @@ int slot_memcpy(ryd_handle* h, int slot, void* dst, const void* src, size_t byte
 }
 
 // One output array of a partitioned run: `rows` rows of `per_point` doubles per point.
+// stride > per_point (one row only): the caller's points are `stride` doubles apart (the
+// Jacobian of ryd_run_schedule_kets with ld_jac > 4 n_seg); the device copy stays packed.
 struct HostOut {
   double* host;
   int64_t ld;
   int rows;
   int per_point;
+  int64_t stride = 0;
 };
 
 // A second per-point input of a partitioned run (the schedule table of ryd_run_schedule):
@@ -3087,6 +3118,13 @@ int run_partitioned(ryd_handle* h, const double* params, int64_t n, int64_t ld_p
     std::vector<CopyTask> unpack;
     for (int j = 0; j < no; ++j) {
       const int64_t w = (int64_t)outs[j].per_point * P.cnt;
+      if (outs[j].stride > outs[j].per_point) {          // point by point, the caller's padding untouched
+        for (int64_t i = 0; i < P.cnt; ++i)
+          unpack.push_back({outs[j].host + (P.off + i) * outs[j].stride,
+                            hb + P.o_out[j] + sizeof(double) * i * outs[j].per_point,
+                            sizeof(double) * outs[j].per_point});
+        continue;
+      }
       for (int r = 0; r < outs[j].rows; ++r)
         unpack.push_back({outs[j].host + (int64_t)r * outs[j].ld + (int64_t)outs[j].per_point * P.off,
                           hb + P.o_out[j] + sizeof(double) * r * w, sizeof(double) * w});
@@ -3343,6 +3381,56 @@ int ryd_run_schedule(ryd_handle* h, const ryd_sched_desc* desc, const double* pa
           hipStream_t s) {
         return launch_schedule(desc, dp, cnt, ldp, tab.dev, ld_sched, out_state ? o[0] : nullptr, 4 * cnt, o.back(),
                                cnt, dst, s);
+      },
+      kms, hms, dms, &tab);
+  if (rc) return rc;
+  fill_stats(stats, h, kms, hms, dms, out_summary, ld_summary, n, RYD_S_NMV_USEFUL, RYD_S_NMV_EXEC);
+  return RYD_OK;
+}
+
+int ryd_run_schedule_kets_device(ryd_handle* h, int slot, const ryd_sched_desc* desc, const double* d_params,
+                                 int64_t n, int64_t ld_params, const double* d_sched, int64_t ld_sched,
+                                 double* d_state, int64_t ld_state, double* d_summary, int64_t ld_summary,
+                                 double* d_jac, int64_t ld_jac, uint32_t* d_status, void* stream,
+                                 float* elapsed_ms) {
+  return on_slot(
+      h, slot, stream, elapsed_ms,
+      [&] {
+        return validate_schedule_kets(desc, d_sched, n, ld_params, ld_sched, ld_state, ld_summary, d_state != nullptr,
+                                      ld_jac, d_jac != nullptr);
+      },
+      [&](hipStream_t s) {
+        return launch_schedule_kets(desc, d_params, n, ld_params, d_sched, ld_sched, d_state, ld_state, d_summary,
+                                    ld_summary, d_jac, ld_jac, d_status, s);
+      });
+}
+
+int ryd_run_schedule_kets(ryd_handle* h, const ryd_sched_desc* desc, const double* params, int64_t n,
+                          int64_t ld_params, const double* sched, int64_t ld_sched, double* out_state,
+                          int64_t ld_state, double* out_summary, int64_t ld_summary, double* out_jac,
+                          int64_t ld_jac, uint32_t* out_status, ryd_stats* stats) {
+  // the descriptor first, so that each refusal reports its own reason with or without a handle
+  int rc = validate_schedule_kets(desc, sched, n, ld_params, ld_sched, ld_state, ld_summary, out_state != nullptr,
+                                  ld_jac, out_jac != nullptr);
+  if (rc) return rc;
+  if (!h) return fail(RYD_ERR_INVALID, "handle is NULL");
+  if (n > 0 && (!params || !out_summary || !out_status)) return fail(RYD_ERR_INVALID, "NULL buffer");
+  // the Jacobian travels out as the table travels in: a slot's rows are one contiguous block
+  // of the caller's array (packed on the device: its leading dimension there is 4 n_seg)
+  const int jw = RYD_SC_NFIELD * desc->n_seg;
+  std::vector<HostOut> outs;
+  if (out_state) outs.push_back({out_state, ld_state, ryd_state_width(RYD_EVOL_KET, 3), 4});
+  if (out_jac) outs.push_back({out_jac, 0, 1, jw, ld_jac});
+  outs.push_back({out_summary, ld_summary, RYD_NSUMMARY, 1});
+  const int ij = out_state ? 1 : 0;
+  HostIn tab = {sched, ld_sched, (int64_t)RYD_SC_NFIELD * desc->n_seg, (desc->flags & RYD_SCHED_SHARED) != 0};
+  double kms, hms, dms;
+  rc = run_partitioned(
+      h, params, n, ld_params, outs, out_status,
+      [&](const double* dp, int64_t cnt, int64_t ldp, int64_t, const std::vector<double*>& o, uint32_t* dst,
+          hipStream_t s) {
+        return launch_schedule_kets(desc, dp, cnt, ldp, tab.dev, ld_sched, out_state ? o[0] : nullptr, 4 * cnt,
+                                    o.back(), cnt, out_jac ? o[ij] : nullptr, jw, dst, s);
       },
       kms, hms, dms, &tab);
   if (rc) return rc;

@@ -99,6 +99,8 @@ class EngineResult:
     matvec_useful: float
     matvec_exec: float
     dim: int = 3
+    # run_schedule_kets(jacobian=True): d a01 / d phi_s and d a11 / d phi_s, complex (n, 2, n_seg)
+    phase_jacobian: Optional[np.ndarray] = None
 
     def col(self, name: str) -> np.ndarray:
         return self.summary[N.S[name]]
@@ -237,6 +239,12 @@ def schedule_desc(params: np.ndarray, sched: np.ndarray) -> Tuple[N.SchedDesc, n
     d.n_seg = tab.shape[-1]
     d.flags = N.FLAG_SYMMETRIC_ATOMS | (N.RYD_SCHED_SHARED if tab.ndim == 2 else 0)
     return d, tab, N.SC_NFIELD * tab.shape[-1]
+
+
+def complex_jacobian(jac: Optional[np.ndarray]) -> Optional[np.ndarray]:
+    """The library's Jacobian rows (n, 4, n_seg) -- Re, Im of d a01, Re, Im of d a11 -- as the
+    complex (n, 2, n_seg) of ``EngineResult.phase_jacobian``; None stays None."""
+    return None if jac is None else jac[:, 0::2] + 1j * jac[:, 1::2]
 
 
 def check_coherence_dim(params: np.ndarray, dim: int) -> None:
@@ -382,6 +390,34 @@ class Engine:
             status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(st)))
         return EngineResult("lindblad", n, state, summ, status, st.kernel_ms, st.h2d_ms, st.d2h_ms,
                             st.matvec_useful, st.matvec_exec, 3)
+
+    def run_schedule_kets(self, params: np.ndarray, sched: np.ndarray, *, states: bool = True,
+                          jacobian: bool = False) -> EngineResult:
+        """The caller's own pulse without noise, as kets (ryd_run_schedule_kets): ``sched`` as
+        ``run_schedule`` takes it; the rate columns of ``params`` are checked and otherwise
+        ignored.  The result is that of ``run(..., "ket")``.  With ``jacobian`` its
+        ``phase_jacobian`` is the complex array (n, 2, n_seg) of d a01 / d phi_s (index 0) and
+        d a11 / d phi_s (index 1), a01 = <01|psi_01>, a11 = <11|psi_11>
+        (``pulse_schedules.overlaps(result.summary)``); state, summary and status do not depend on it.
+        ``states=False`` is a summary-only run."""
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        if params.shape[0] != N.NPARAM:
+            raise ValueError(f"params must have shape ({N.NPARAM}, n)")
+        n = params.shape[1]
+        desc, tab, ld = schedule_desc(params, sched)
+        state = np.empty((N.STATE_WIDTH["ket"], 4 * n), dtype=np.float64) if states else None
+        summ = np.empty((N.NSUMMARY, n), dtype=np.float64)
+        jac = np.empty((n, N.SC_NFIELD, desc.n_seg), dtype=np.float64) if jacobian else None
+        status = np.zeros(n, dtype=np.uint32)
+        st = N.Stats()
+        dptr = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        N.check(self.lib.ryd_run_schedule_kets(
+            self.handle, ctypes.byref(desc), dptr(params), n, n, dptr(tab), ld,
+            dptr(state) if states else None, 4 * n, dptr(summ), n,
+            dptr(jac) if jacobian else None, N.SC_NFIELD * desc.n_seg,
+            status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(st)))
+        return EngineResult("ket", n, state, summ, status, st.kernel_ms, st.h2d_ms, st.d2h_ms,
+                            st.matvec_useful, st.matvec_exec, 3, complex_jacobian(jac))
 
     def last_timeline(self) -> Dict[str, Any]:
         """ryd_last_timeline: host staging times and the per-slot HIP-event timeline of the
@@ -606,6 +642,74 @@ class ScheduleDeviceBatch:
         N.check(lib.ryd_memcpy_d2h(h, s, status.ctypes.data, self.d_status, status.nbytes))
         return EngineResult("lindblad", self.n, state, summ, status, 0.0, 0.0, 0.0,
                             summ[N.S["NMV_USEFUL"]].sum(), summ[N.S["NMV_EXEC"]].sum(), 3)
+
+    def free(self):
+        for p in self._bufs:
+            self.eng.lib.ryd_free(self.eng.handle, self.slot, p)
+        self._bufs = []
+
+
+class ScheduleKetDeviceBatch:
+    """A noise-free schedule run as kets (ryd_run_schedule_kets_device) with parameters and table
+    resident in HBM on one device slot, for timed re-runs, in the manner of
+    ``ScheduleDeviceBatch``; ``sched``, ``states`` and ``jacobian`` as
+    ``Engine.run_schedule_kets`` takes them."""
+
+    def __init__(self, engine: Engine, params: np.ndarray, sched: np.ndarray, slot: int = 0,
+                 states: bool = True, jacobian: bool = False):
+        self.eng, self.slot = engine, slot
+        self.states, self.jacobian = states, jacobian   # False: no buffer, NULL is passed
+        lib = engine.lib
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        if params.shape[0] != N.NPARAM:
+            raise ValueError(f"params must have shape ({N.NPARAM}, n)")
+        self.n = n = params.shape[1]
+        self.desc, tab, self.ld_sched = schedule_desc(params, sched)
+        self.width = N.STATE_WIDTH["ket"]
+        self.ld_jac = N.SC_NFIELD * self.desc.n_seg
+        self._bufs = []
+
+        def alloc(nbytes):
+            p = ctypes.c_void_p()
+            N.check(lib.ryd_malloc(engine.handle, slot, max(nbytes, 16), ctypes.byref(p)))
+            self._bufs.append(p)
+            return p
+        self.d_params = alloc(params.nbytes)
+        self.d_sched = alloc(tab.nbytes)
+        self.d_state = alloc(8 * self.width * 4 * n) if states else None
+        self.d_summary = alloc(8 * N.NSUMMARY * n)
+        self.d_jac = alloc(8 * self.ld_jac * n) if jacobian else None
+        self.d_status = alloc(4 * n)
+        N.check(lib.ryd_memcpy_h2d(engine.handle, slot, self.d_params, params.ctypes.data, params.nbytes))
+        N.check(lib.ryd_memcpy_h2d(engine.handle, slot, self.d_sched, tab.ctypes.data, tab.nbytes))
+
+    def launch(self, timed: bool = False) -> float:
+        """Enqueue one propagation of the whole batch; with ``timed`` wait and return the
+        kernel's device time (HIP events on the launch stream)."""
+        ms = ctypes.c_float(0.0)
+        N.check(self.eng.lib.ryd_run_schedule_kets_device(
+            self.eng.handle, self.slot, ctypes.byref(self.desc), self.d_params, self.n, self.n,
+            self.d_sched, self.ld_sched, self.d_state, 4 * self.n, self.d_summary, self.n,
+            self.d_jac, self.ld_jac, self.d_status, None, ctypes.byref(ms) if timed else None))
+        return float(ms.value)
+
+    def synchronize(self):
+        N.check(self.eng.lib.ryd_synchronize(self.eng.handle))
+
+    def fetch(self) -> EngineResult:
+        lib, h, s = self.eng.lib, self.eng.handle, self.slot
+        state = np.zeros((self.width, 4 * self.n)) if self.states else None
+        summ = np.zeros((N.NSUMMARY, self.n))
+        jac = np.zeros((self.n, N.SC_NFIELD, self.desc.n_seg)) if self.jacobian else None
+        status = np.zeros(self.n, dtype=np.uint32)
+        if self.states:
+            N.check(lib.ryd_memcpy_d2h(h, s, state.ctypes.data, self.d_state, state.nbytes))
+        if self.jacobian:
+            N.check(lib.ryd_memcpy_d2h(h, s, jac.ctypes.data, self.d_jac, jac.nbytes))
+        N.check(lib.ryd_memcpy_d2h(h, s, summ.ctypes.data, self.d_summary, summ.nbytes))
+        N.check(lib.ryd_memcpy_d2h(h, s, status.ctypes.data, self.d_status, status.nbytes))
+        return EngineResult("ket", self.n, state, summ, status, 0.0, 0.0, 0.0,
+                            summ[N.S["NMV_USEFUL"]].sum(), summ[N.S["NMV_EXEC"]].sum(), 3, complex_jacobian(jac))
 
     def free(self):
         for p in self._bufs:

@@ -20,7 +20,7 @@ from typing import Callable, Optional, Sequence, Union
 
 import numpy as np
 
-from ._native import SC, SC_NFIELD, SCHED_MAX_SEG
+from ._native import S, SC, SC_NFIELD, SCHED_MAX_SEG
 
 ArrayLike = Union[float, Sequence[float], np.ndarray]
 
@@ -117,3 +117,108 @@ def from_functions(amp: Union[float, Callable], phase: Union[float, Callable], d
         v = f(mid) if callable(f) else f
         return np.broadcast_to(np.asarray(v, dtype=np.float64), (n_seg,))
     return validate_schedule(assemble(np.full(n_seg, du), sample(amp), sample(phase), sample(delta)))
+
+
+# ---- the table as an optimiser's parameterisation: phase gradients of the noise-free gate
+def overlaps(summary: np.ndarray):
+    """(a01, a11), complex (n,), from the summary rows of a ket run: a01 = <01|psi_01> is input
+    1 of OV_RE0 / OV_IM0, a11 = <11|psi_11> input 3."""
+    re, im = S["OV_RE0"], S["OV_IM0"]
+    return summary[re + 1] + 1j * summary[im + 1], summary[re + 3] + 1j * summary[im + 3]
+
+
+def gate_fidelity_and_gradient(a01: np.ndarray, a11: np.ndarray, J: np.ndarray, which: str = "avg_gate"):
+    """``noise_models.gate_fidelity`` of a noise-free identical-atom gate from its two diagonal
+    overlaps a01 = <01|psi_01> (= <10|psi_10>) and a11 = <11|psi_11> (complex, shape (n,)), and
+    its derivative with respect to every segment's phase from ``J`` (complex (n, 2, n_seg),
+    ``EngineResult.phase_jacobian``: d a01 / d phi_s, d a11 / d phi_s).  ``which``: "process"
+    or "avg_gate".  Returns (F (n,), dF/dphi (n, n_seg)).
+
+    With the local-Z phases (alpha, beta) that ``cz_phase_fit`` returns,
+    T = 1 + a01 (e^{-i beta} + e^{-i alpha}) - a11 e^{-i (alpha + beta)}, F_pro = |T|^2 / 16,
+    survival = (1 + 2 |a01|^2 + |a11|^2) / 4 and F_avg = (4 F_pro + survival) / 5.  The fitted
+    phases maximise F_pro, a stationary point, so the partial derivative at fixed (alpha, beta)
+    is the whole derivative."""
+    from . import noise_models as NM
+    if which not in ("process", "avg_gate"):
+        raise ValueError(f'which must be "process" or "avg_gate", not {which!r}')
+    a01 = np.atleast_1d(np.asarray(a01, dtype=np.complex128))
+    a11 = np.atleast_1d(np.asarray(a11, dtype=np.complex128))
+    J = np.asarray(J, dtype=np.complex128)
+    n = a01.shape[0]
+    if a11.shape != (n,) or J.ndim != 3 or J.shape[:2] != (n, 2):
+        raise ValueError(f"need a01 (n,), a11 (n,) and J (n, 2, n_seg), got {a01.shape}, {a11.shape}, {J.shape}")
+    # the qubit block of the four output kets: only the diagonal amplitudes are in it
+    psi = np.zeros((n, 4, 9), dtype=np.complex128)
+    psi[:, 0, 0] = 1.0
+    psi[:, 1, 1] = a01
+    psi[:, 2, 3] = a01
+    psi[:, 3, 4] = a11
+    al, be = NM.cz_phase_fit(NM.ket_maps(psi))
+    w01 = np.exp(-1j * be) + np.exp(-1j * al)
+    w11 = -np.exp(-1j * (al + be))
+    T = 1.0 + a01 * w01 + a11 * w11
+    fpro = np.abs(T) ** 2 / 16
+    dT = w01[:, None] * J[:, 0] + w11[:, None] * J[:, 1]
+    dpro = 2.0 * np.real(np.conj(T)[:, None] * dT) / 16
+    if which == "process":
+        return fpro, dpro
+    surv = (1.0 + 2.0 * np.abs(a01) ** 2 + np.abs(a11) ** 2) / 4
+    dsurv = (4.0 * np.real(np.conj(a01)[:, None] * J[:, 0]) + 2.0 * np.real(np.conj(a11)[:, None] * J[:, 1])) / 4
+    return (4 * fpro + surv) / 5, (4 * dpro + dsurv) / 5
+
+
+def optimize_phases(params: np.ndarray, sched0: np.ndarray, *, which: str = "avg_gate", maxiter: int = 200,
+                    engine=None) -> dict:
+    """Optimise the phase field of noise-free schedules by L-BFGS-B on exact gradients.
+
+    Every point of ``params`` (NPARAM, n) is its own start, with its own parameters and its own
+    table (``sched0``: (n, 4, n_seg), or (4, n_seg) copied to every point); only the phases
+    move.  The starts are optimised together, as ONE problem: the objective is the separable
+    sum of the points' infidelities 1 - F (``gate_fidelity_and_gradient``) over the
+    concatenated n n_seg phases, and every function evaluation is exactly one
+    ``Engine.run_schedule_kets(..., states=False, jacobian=True)`` call for all the starts.
+    The sum is separable but the optimiser is not: one line search, one step length and one
+    L-BFGS history serve all the starts, so a start's path depends on its companions, and the
+    run ends on the sum's criteria, not on each start's own.  (Per-start optimiser state is
+    not kept.)
+
+    Returns a dict: ``sched`` (n, 4, n_seg) the final tables, ``F_start`` and ``F_final`` (n,)
+    the fidelity ``which`` of every point at ``sched0`` and at ``sched``, ``nfev``,
+    ``engine_calls``, ``nit``, ``success`` and ``message`` (scipy's)."""
+    import hashlib
+
+    from scipy.optimize import minimize
+
+    from . import engine as E
+    params = np.ascontiguousarray(params, dtype=np.float64)
+    n = params.shape[1]
+    tab = validate_schedule(sched0, n if np.ndim(sched0) == 3 else None)
+    if tab.ndim == 2:
+        tab = np.ascontiguousarray(np.broadcast_to(tab, (n,) + tab.shape))
+    tab = tab.copy()
+    n_seg = tab.shape[-1]
+    eng = engine if engine is not None else E.Engine()
+    calls = [0]
+    seen = {}                                # digest of an evaluated phase vector -> its F (n,)
+    first = []
+
+    def fun(phi):
+        tab[:, SC["PHASE"], :] = phi.reshape(n, n_seg)
+        r = eng.run_schedule_kets(params, tab, states=False, jacobian=True)
+        calls[0] += 1
+        a01, a11 = overlaps(r.summary)
+        F, dF = gate_fidelity_and_gradient(a01, a11, r.phase_jacobian, which)
+        if not first:
+            first.append(F)
+        seen[hashlib.sha1(phi.tobytes()).digest()] = F
+        return float(np.sum(1.0 - F)), -dF.reshape(-1)
+
+    res = minimize(fun, tab[:, SC["PHASE"], :].reshape(-1).copy(), jac=True, method="L-BFGS-B",
+                   options=dict(maxiter=maxiter))
+    # the returned point is one of those evaluated: its F needs no further engine call
+    x = np.ascontiguousarray(res.x, dtype=np.float64)
+    tab[:, SC["PHASE"], :] = x.reshape(n, n_seg)
+    F_final = seen[hashlib.sha1(x.tobytes()).digest()]
+    return dict(sched=tab, F_start=first[0], F_final=F_final, nfev=int(res.nfev), engine_calls=calls[0],
+                nit=int(res.nit), success=bool(res.success), message=str(res.message))
