@@ -445,6 +445,34 @@ int ryd_run_schedule_kets_device(ryd_handle* h, int slot, const ryd_sched_desc* 
                                  double* d_jac, int64_t ld_jac,
                                  uint32_t* d_status, void* stream, float* elapsed_ms);
 
+/* The same run with the derivatives of the two overlaps with respect to all four fields of
+ * every segment, from one backward walk (ket_sched_ctl_kernel):
+ *     jac[i * ld_jac + (4 * f + c) * n_seg + s] = d a / d field_f of segment s,
+ *     f = RYD_SC_X .. RYD_SC_DELTA (the table's order and units), c as above,
+ *     ld_jac >= 16 * n_seg, out_jac / d_jac not NULL.
+ * State, summary, status and the RYD_SC_PHASE block are those of ryd_run_schedule_kets bit for
+ * bit.  A segment of zero duration has the one-sided d a / d x_s (in general not zero) and
+ * exact zeros in the other three fields; a step-capped segment and every segment of a
+ * BAD_INPUT point have exact zeros in all four.  Refused before any GPU call, descriptor first,
+ * by the rules of ryd_run_schedule_kets, then a NULL Jacobian, then ld_jac < 16 n_seg
+ * (RYD_ERR_INVALID). */
+int ryd_run_schedule_kets_ctl(ryd_handle* h, const ryd_sched_desc* desc,
+                              const double* params, int64_t n, int64_t ld_params,
+                              const double* sched, int64_t ld_sched,
+                              double* out_state, int64_t ld_state,
+                              double* out_summary, int64_t ld_summary,
+                              double* out_jac, int64_t ld_jac,
+                              uint32_t* out_status, ryd_stats* stats);
+/* Device buffers on slot `slot` (d_jac: (n - 1) * ld_jac + 16 * n_seg doubles); d_state may
+ * be NULL. */
+int ryd_run_schedule_kets_ctl_device(ryd_handle* h, int slot, const ryd_sched_desc* desc,
+                                     const double* d_params, int64_t n, int64_t ld_params,
+                                     const double* d_sched, int64_t ld_sched,
+                                     double* d_state, int64_t ld_state,
+                                     double* d_summary, int64_t ld_summary,
+                                     double* d_jac, int64_t ld_jac,
+                                     uint32_t* d_status, void* stream, float* elapsed_ms);
+
 /* Process-map coherences (layout above).  Chebyshev state-vector method; any
  * protocol, either evolution value (rates may be zero).  Host-buffer form
  * range-partitions like ryd_run_batch; status bits as ryd_run_batch. */

@@ -76,7 +76,8 @@ EXPORTED = ("ryd_abi_version", "ryd_last_error", "ryd_param_count", "ryd_summary
             "ryd_malloc", "ryd_free", "ryd_memcpy_h2d", "ryd_memcpy_d2h", "ryd_synchronize", "ryd_evolve_generic",
             "ryd_derive", "ryd_derive_device", "ryd_run_schedule", "ryd_run_schedule_device",
             "ryd_run_schedule_coherences", "ryd_run_schedule_coherences_device",
-            "ryd_run_schedule_kets", "ryd_run_schedule_kets_device")
+            "ryd_run_schedule_kets", "ryd_run_schedule_kets_device",
+            "ryd_run_schedule_kets_ctl", "ryd_run_schedule_kets_ctl_device")
 
 # device derivation (ryd_derive): input fields, species-table columns, flags, diagnostic columns
 DV = dict(SPECIES=0, N_RYD=1, P1=2, P2=3, W1=4, W2=5, DELTA_E=6, LW1=7, LW2=8, TW_POWER=9, TW_WAIST=10,
@@ -196,6 +197,9 @@ def load() -> ctypes.CDLL:
         lib.ryd_run_schedule_kets_device.argtypes = [vp, ctypes.c_int, ctypes.POINTER(SchedDesc), vp, i64, i64, vp,
                                                      i64, vp, i64, vp, i64, vp, i64, vp, vp,
                                                      ctypes.POINTER(ctypes.c_float)]
+        # the same arguments; the Jacobian is required and 16 n_seg wide
+        lib.ryd_run_schedule_kets_ctl.argtypes = list(lib.ryd_run_schedule_kets.argtypes)
+        lib.ryd_run_schedule_kets_ctl_device.argtypes = list(lib.ryd_run_schedule_kets_device.argtypes)
         lib.ryd_run_coherences.argtypes = [vp, ctypes.POINTER(BatchDesc), dp, i64, i64, dp, i64,
                                            ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(Stats)]
         lib.ryd_run_coherences_device.argtypes = [vp, ctypes.c_int, ctypes.POINTER(BatchDesc), vp, i64,

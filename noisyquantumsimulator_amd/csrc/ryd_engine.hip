@@ -2654,6 +2654,28 @@ int launch_schedule_kets(const ryd_sched_desc* d, const double* dp, int64_t n, i
                       dsc, ld, nseg, ds, lds, dm, ldm, dstat);
 }
 
+// ryd_run_schedule_kets_ctl[_device]: validate_schedule_kets' rules, with the Jacobian required
+// and four fields wide
+int validate_schedule_kets_ctl(const ryd_sched_desc* d, const double* sched, int64_t n, int64_t ldp, int64_t ldsc,
+                               int64_t lds, int64_t ldm, bool has_state, const double* jac, int64_t ldj) {
+  if (int rc = validate_schedule_kets(d, sched, n, ldp, ldsc, lds, ldm, has_state, 0, false)) return rc;
+  if (!jac) return fail(RYD_ERR_INVALID, "the control Jacobian is NULL");
+  if (ldj < 4 * (int64_t)RYD_SC_NFIELD * d->n_seg) return fail(RYD_ERR_INVALID, "ld_jac is smaller than 16 n_seg");
+  return RYD_OK;
+}
+
+// One noise-free schedule batch with the Jacobian of all four fields (ket_sched_ctl_kernel)
+int launch_schedule_kets_ctl(const ryd_sched_desc* d, const double* dp, int64_t n, int64_t ldp, const double* dsc,
+                             int64_t ldsc, double* ds, int64_t lds, double* dm, int64_t ldm, double* dj, int64_t ldj,
+                             uint32_t* dstat, hipStream_t stream) {
+  if (n == 0) return RYD_OK;
+  if (!ds) lds = 0;
+  const int64_t ld = (d->flags & RYD_SCHED_SHARED) ? 0 : ldsc;
+  const int nseg = d->n_seg;
+  return launch_typed(ds ? ket_sched_ctl_kernel<true> : ket_sched_ctl_kernel<false>, (n + S16_PPW - 1) / S16_PPW,
+                      S16_BLOCK, 0, stream, dp, n, ldp, dsc, ld, nseg, ds, lds, dm, ldm, dj, ldj, dstat);
+}
+
 // RYD_COH_PROP=0 selects coherence_cheb_kernel for every protocol (A/B and cross-check runs)
 bool coh_prop_enabled() { return !is_off(getenv("RYD_COH_PROP")); }
 
@@ -3431,6 +3453,54 @@ int ryd_run_schedule_kets(ryd_handle* h, const ryd_sched_desc* desc, const doubl
           hipStream_t s) {
         return launch_schedule_kets(desc, dp, cnt, ldp, tab.dev, ld_sched, out_state ? o[0] : nullptr, 4 * cnt,
                                     o.back(), cnt, out_jac ? o[ij] : nullptr, jw, dst, s);
+      },
+      kms, hms, dms, &tab);
+  if (rc) return rc;
+  fill_stats(stats, h, kms, hms, dms, out_summary, ld_summary, n, RYD_S_NMV_USEFUL, RYD_S_NMV_EXEC);
+  return RYD_OK;
+}
+
+int ryd_run_schedule_kets_ctl_device(ryd_handle* h, int slot, const ryd_sched_desc* desc, const double* d_params,
+                                     int64_t n, int64_t ld_params, const double* d_sched, int64_t ld_sched,
+                                     double* d_state, int64_t ld_state, double* d_summary, int64_t ld_summary,
+                                     double* d_jac, int64_t ld_jac, uint32_t* d_status, void* stream,
+                                     float* elapsed_ms) {
+  return on_slot(
+      h, slot, stream, elapsed_ms,
+      [&] {
+        return validate_schedule_kets_ctl(desc, d_sched, n, ld_params, ld_sched, ld_state, ld_summary,
+                                          d_state != nullptr, d_jac, ld_jac);
+      },
+      [&](hipStream_t s) {
+        return launch_schedule_kets_ctl(desc, d_params, n, ld_params, d_sched, ld_sched, d_state, ld_state, d_summary,
+                                        ld_summary, d_jac, ld_jac, d_status, s);
+      });
+}
+
+int ryd_run_schedule_kets_ctl(ryd_handle* h, const ryd_sched_desc* desc, const double* params, int64_t n,
+                              int64_t ld_params, const double* sched, int64_t ld_sched, double* out_state,
+                              int64_t ld_state, double* out_summary, int64_t ld_summary, double* out_jac,
+                              int64_t ld_jac, uint32_t* out_status, ryd_stats* stats) {
+  int rc = validate_schedule_kets_ctl(desc, sched, n, ld_params, ld_sched, ld_state, ld_summary,
+                                      out_state != nullptr, out_jac, ld_jac);
+  if (rc) return rc;
+  if (!h) return fail(RYD_ERR_INVALID, "handle is NULL");
+  if (n > 0 && (!params || !out_summary || !out_status)) return fail(RYD_ERR_INVALID, "NULL buffer");
+  // as ryd_run_schedule_kets, four fields wide: packed on the device, leading dimension 16 n_seg
+  const int jw = 4 * RYD_SC_NFIELD * desc->n_seg;
+  std::vector<HostOut> outs;
+  if (out_state) outs.push_back({out_state, ld_state, ryd_state_width(RYD_EVOL_KET, 3), 4});
+  outs.push_back({out_jac, 0, 1, jw, ld_jac});
+  outs.push_back({out_summary, ld_summary, RYD_NSUMMARY, 1});
+  const int ij = out_state ? 1 : 0;
+  HostIn tab = {sched, ld_sched, (int64_t)RYD_SC_NFIELD * desc->n_seg, (desc->flags & RYD_SCHED_SHARED) != 0};
+  double kms, hms, dms;
+  rc = run_partitioned(
+      h, params, n, ld_params, outs, out_status,
+      [&](const double* dp, int64_t cnt, int64_t ldp, int64_t, const std::vector<double*>& o, uint32_t* dst,
+          hipStream_t s) {
+        return launch_schedule_kets_ctl(desc, dp, cnt, ldp, tab.dev, ld_sched, out_state ? o[0] : nullptr, 4 * cnt,
+                                        o.back(), cnt, o[ij], jw, dst, s);
       },
       kms, hms, dms, &tab);
   if (rc) return rc;

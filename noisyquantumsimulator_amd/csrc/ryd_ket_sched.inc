@@ -39,9 +39,17 @@
 // as one 128-byte piece of jac[i ld_jac + c n_seg + s], c = Re da01, Im da01, Re da11, Im da11.
 // A skipped segment and every segment of an invalid point get exact zeros.
 //
+// Control Jacobian (ket_sched_ctl_kernel, ryd_run_schedule_kets_ctl).  The same forward pass
+// and one backward walk that writes the derivatives with respect to all four fields,
+// jac[i ld_jac + (4 f + c) n_seg + s], f = RYD_SC_X .. RYD_SC_DELTA; its phase block, state,
+// summary and status are ket_sched_jac_kernel's bit for bit.  The formulas stand with the code
+// (ket_ctl_block, and the walk at the end of ket_sched_body).
+//
 // Registers (make resource-usage): 201 / 205 VGPRs forward (STATE false / true), 207 / 209 with
 // the Jacobian, no scratch, no LDS: 2 waves per SIMD.  An amdgpu_waves_per_eu(3, 8) budget of
-// 168 spills 116-132 bytes per lane around ket_blocks_build, so none is set.
+// 168 spills 116-132 bytes per lane around ket_blocks_build, so none is set.  The control
+// kernel: 253 VGPRs, no scratch, 18,432 bytes of LDS (derivative rows, chunk results, and the
+// walk's state parked across a build), 2 waves per SIMD under amdgpu_waves_per_eu(2, 8).
 
 // lane r takes the value of lane (r - 1) mod 16 of its row: row_ror:1
 __device__ __forceinline__ double row_ror1(double v) { return dpp32x2<0x121>(v); }
@@ -114,7 +122,212 @@ __device__ __forceinline__ void ket_sched_g(double nu, double w, double (&g)[4])
   g[3] = (row_bcast<6>(pc) + row_bcast<7>(pc)) + 2.0 * (row_bcast<8>(pc) + row_bcast<9>(pc));
 }
 
-template <bool STATE, bool JAC>
+// ---- the control Jacobian (ket_sched_ctl_kernel): duration, amplitude, phase, detuning
+// With H_r = Q diag(lambda) Q^T the derivative of U' = exp(-i H_r dt) along H_theta is
+//   dU'/dtheta = Q [ (Q^T H_theta Q) o Phi ] Q^T,
+//   Phi_kl = -i dt e^{-i (lambda_k + lambda_l) dt / 2} sinc((lambda_k - lambda_l) dt / 2),
+// finite for every gap (Phi_kk = -i dt e^{-i lambda_k dt}); H_a is the coupling pattern (cpl on
+// the off-diagonals next to the diagonal), H_Delta = -diag(0, 1[, 2]).
+
+// sin h / h; below the switch its series, whose next term is h^6 / 5040 < 2e-22
+constexpr double KET_SINC_SWITCH = 1e-3;
+__device__ __forceinline__ double ket_sinc(double h) {
+  const double h2 = h * h;
+  const double ser = fma(h2, fma(h2, 1.0 / 120.0, -1.0 / 6.0), 1.0);
+  return fabs(h) < KET_SINC_SWITCH ? ser : sin(h) / h;
+}
+
+// The eigen data of one N x N block (the upper left of Q): H_r = Q diag(lambda) Q^T, and Phi's
+// upper triangle in KetBlocks' order (00 01 [02] 11 [12 22])
+struct KetEig {
+  double Q[3][3];
+  double P[6][2];
+};
+
+// Phi from the eigenvalues; (er, ei)_k = e^{-i lambda_k dt}
+template <int N>
+__device__ __forceinline__ void ket_ctl_phi(KetEig& E, const double (&lam)[3], const double (&er)[3],
+                                            const double (&ei)[3], double dt) {
+  int e = 0;
+#pragma unroll
+  for (int k = 0; k < N; ++k)
+#pragma unroll
+    for (int l = k; l < N; ++l, ++e) {
+      if (k == l) {
+        E.P[e][0] = dt * ei[k];
+        E.P[e][1] = -dt * er[k];
+      } else {
+        double sn, cs;
+        sincos(0.5 * (lam[k] + lam[l]) * dt, &sn, &cs);
+        const double sc = dt * ket_sinc(0.5 * (lam[k] - lam[l]) * dt);
+        E.P[e][0] = -sc * sn;
+        E.P[e][1] = -sc * cs;
+      }
+    }
+}
+
+// Row i of dU'/dtheta (the lane's own; any other i gives zeros) in the real form of
+// ket_sched_row: out[2 j], out[2 j + 1] for column j.  F = 0: theta = a, cpl on the coupling
+// pattern; F = 1: theta = Delta.
+template <int N, int F>
+__device__ __forceinline__ void ket_ctl_row(const KetEig& E, double cpl, int i, bool im, double (&out)[2 * N]) {
+  double M[N][N];                            // Q^T H_theta Q
+#pragma unroll
+  for (int k = 0; k < N; ++k)
+#pragma unroll
+    for (int l = k; l < N; ++l) {
+      double m = 0.0;
+      if constexpr (F == 0) {
+#pragma unroll
+        for (int c = 0; c + 1 < N; ++c) m = fma(E.Q[c][k], E.Q[c + 1][l], fma(E.Q[c + 1][k], E.Q[c][l], m));
+        m *= cpl;
+      } else {
+#pragma unroll
+        for (int c = 1; c < N; ++c) m = fma(-(double)c * E.Q[c][k], E.Q[c][l], m);
+      }
+      M[k][l] = M[l][k] = m;
+    }
+  double q[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    q[k] = 0.0;
+#pragma unroll
+    for (int c = 0; c < N; ++c) q[k] = (i == c) ? E.Q[c][k] : q[k];
+  }
+  // v_l = sum_k q_k (M o Phi)_kl, then dU'[i][j] = sum_l v_l Q[j][l]
+  double vr[N], vi[N];
+#pragma unroll
+  for (int l = 0; l < N; ++l) {
+    vr[l] = vi[l] = 0.0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      const int lo = k < l ? k : l, hi = k < l ? l : k;
+      const int e = lo * N - lo * (lo - 1) / 2 + (hi - lo);
+      const double qm = q[k] * M[k][l];
+      vr[l] = fma(qm, E.P[e][0], vr[l]);
+      vi[l] = fma(qm, E.P[e][1], vi[l]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    double ar = 0.0, ai = 0.0;
+#pragma unroll
+    for (int l = 0; l < N; ++l) {
+      ar = fma(vr[l], E.Q[j][l], ar);
+      ai = fma(vi[l], E.Q[j][l], ai);
+    }
+    out[2 * j] = im ? ai : ar;
+    out[2 * j + 1] = im ? ar : -ai;
+  }
+}
+
+// ket_blocks_build (ryd_engine.hip) statement for statement, so that B has its bits, and beside
+// it the eigen data of both blocks.  The 2 x 2 block's eigenvectors come from one Jacobi
+// rotation, exact for a 2 x 2 matrix.
+__device__ __forceinline__ void ket_blocks_build_ctl(KetBlocks& B, KetEig& E2, KetEig& E3, double a, double dl,
+                                                     double dt, double d1, double V) {
+  B.a = a;
+  B.dl = dl;
+  B.dt = dt;
+  {
+    const double c = 0.5 * (d1 - dl), h = 0.5 * (d1 + dl), w = 0.5 * a;
+    const double r = sqrt(fma(h, h, w * w));
+    double sr, cr, sc, cc;
+    sincos(r * dt, &sr, &cr);
+    sincos(c * dt, &sc, &cc);
+    const double snc = r > 0.0 ? sr / r : dt;
+    const double m[3][2] = {{cr, -snc * h}, {0.0, -snc * w}, {cr, snc * h}};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      B.u2[k][0] = fma(cc, m[k][0], sc * m[k][1]);
+      B.u2[k][1] = fma(cc, m[k][1], -sc * m[k][0]);
+    }
+    double A[3][3] = {{d1, w, 0.0}, {w, -dl, 0.0}, {0.0, 0.0, 0.0}};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) E2.Q[i][j] = i == j ? 1.0 : 0.0;
+    jacobi_rot(A, E2.Q, 0, 1);
+    const double lam[3] = {A[0][0], A[1][1], 0.0};
+    double er[3] = {1.0, 1.0, 1.0}, ei[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      double sn, cs;
+      sincos(lam[k] * dt, &sn, &cs);
+      er[k] = cs;
+      ei[k] = -sn;
+    }
+    ket_ctl_phi<2>(E2, lam, er, ei, dt);
+  }
+  {
+    const double g = a * 0.70710678118654752440;     // a / sqrt2
+    double A[3][3] = {{2.0 * d1, g, 0.0}, {g, d1 - dl, g}, {0.0, g, V - 2.0 * dl}};
+    double (&Q)[3][3] = E3.Q;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) Q[i][j] = i == j ? 1.0 : 0.0;
+#pragma unroll 1
+    for (int sweep = 0; sweep < 6; ++sweep) {
+      jacobi_rot(A, Q, 0, 1);
+      jacobi_rot(A, Q, 0, 2);
+      jacobi_rot(A, Q, 1, 2);
+    }
+    double er[3], ei[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      double sn, cs;
+      sincos(A[k][k] * dt, &sn, &cs);
+      er[k] = cs;
+      ei[k] = -sn;
+    }
+    const int I[6] = {0, 0, 0, 1, 1, 2}, J[6] = {0, 1, 2, 1, 2, 2};
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+      double re = 0.0, im = 0.0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double w = Q[I[e]][k] * Q[J[e]][k];
+        re = fma(w, er[k], re);
+        im = fma(w, ei[k], im);
+      }
+      B.u3[e][0] = re;
+      B.u3[e][1] = im;
+    }
+    const double lam[3] = {A[0][0], A[1][1], A[2][2]};
+    ket_ctl_phi<3>(E3, lam, er, ei, dt);
+  }
+}
+
+// lane r takes the value of lane (r - 2) mod 16 / (r + 2) mod 16 of its row: row_ror:2, row_ror:14
+__device__ __forceinline__ double row_ror2(double v) { return dpp32x2<0x122>(v); }
+__device__ __forceinline__ double row_rol2(double v) { return dpp32x2<0x12E>(v); }
+
+// nu^T y of both blocks from the lanes' products ps = sg nu y and pc = nu y(partner): o = Re, Im
+// of the 2 x 2 block's sum (lanes 0..3), Re, Im of the 3 x 3 block's (lanes 4..9); every lane of
+// the row gets all four.  `one` is 1.0 in a register (the FMA's second factor).
+__device__ __forceinline__ void ket_ctl_sums(double ps, double pc, double one, double (&o)[4]) {
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#define RYD_CTL_FMAC(acc, src, lane) \
+  "v_fmac_f64_dpp " acc ", " src ", %6 row_newbcast:" #lane " row_mask:0xf bank_mask:0xf\n\t"
+  asm volatile("s_nop 1\n\t"
+               RYD_CTL_FMAC("%0", "%4", 0) RYD_CTL_FMAC("%1", "%5", 0) RYD_CTL_FMAC("%2", "%4", 4)
+               RYD_CTL_FMAC("%3", "%5", 4) RYD_CTL_FMAC("%0", "%4", 1) RYD_CTL_FMAC("%1", "%5", 1)
+               RYD_CTL_FMAC("%2", "%4", 5) RYD_CTL_FMAC("%3", "%5", 5) RYD_CTL_FMAC("%0", "%4", 2)
+               RYD_CTL_FMAC("%1", "%5", 2) RYD_CTL_FMAC("%2", "%4", 6) RYD_CTL_FMAC("%3", "%5", 6)
+               RYD_CTL_FMAC("%0", "%4", 3) RYD_CTL_FMAC("%1", "%5", 3) RYD_CTL_FMAC("%2", "%4", 7)
+               RYD_CTL_FMAC("%3", "%5", 7) RYD_CTL_FMAC("%2", "%4", 8) RYD_CTL_FMAC("%3", "%5", 8)
+               RYD_CTL_FMAC("%2", "%4", 9) "v_fmac_f64_dpp %3, %5, %6 row_newbcast:9 row_mask:0xf bank_mask:0xf"
+               : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3)
+               : "v"(ps), "v"(pc), "v"(one));
+#undef RYD_CTL_FMAC
+  o[0] = a0;
+  o[1] = a1;
+  o[2] = a2;
+  o[3] = a3;
+}
+
+template <bool STATE, bool JAC, bool CTL = false>
 __device__ __forceinline__ void ket_sched_body(const double* __restrict__ prm, int64_t n, int64_t ldp,
                                                const double* __restrict__ sched, int64_t ldsc, int n_seg,
                                                double* __restrict__ st, int64_t lds, double* __restrict__ sm,
@@ -394,6 +607,163 @@ __device__ __forceinline__ void ket_sched_body(const double* __restrict__ prm, i
       }
     }
   }
+
+  // ---- the backward walk for all four fields (ket_sched_ctl_kernel).  The phase block is the
+  // walk above, operation for operation.  In the segment's frame, with w_s, nu_s before the
+  // step and w_{s-1} after it:
+  //   da/dx_s     = -(i / Omega) nu_s^T H_r w_s      (U' commutes with H_r: no propagator
+  //                 derivative; H_r = H0 + a Ha - Delta G from the key, tridiagonal)
+  //   da/da_s     = Omega nu_s^T (dU'/da) w_{s-1},   da/ddelta_s = Omega nu_s^T (dU'/dDelta) w_{s-1}
+  // with each lane's rows of dU'/da and dU'/dDelta kept in LDS ([coefficient][lane]: a lane reads
+  // and writes its own column, conflict-free, no barrier) and memoised with the build.  The
+  // forward pass leaves no derivative rows, so the walk's first applied segment builds.  A segment
+  // of zero duration has the one-sided da/dx_s of the same form in its own phi_s, with nu and w
+  // as they stand (the frame is not committed) and exact zeros elsewhere; a capped segment and an
+  // invalid point get exact zeros in all four fields.
+  if constexpr (CTL) {
+    __shared__ double Drow[20][S16_BLOCK];
+    __shared__ double Jrow[16][S16_BLOCK];   // the chunk's results: lane j's sixteen numbers of segment s0 + j
+    const double hs = 0.70710678118654752440;
+    // (not const: parked with the walk's state across a build)
+    double kqd = (double)kq;
+    double e0 = r < 2 ? d1 : (r < 4 ? 0.0 : (r < 6 ? 2.0 * d1 : (r < 8 ? d1 : (r < 10 ? V : 0.0))));
+    double cl = (r == 2 || r == 3) ? 0.5 : ((r >= 6 && r < 10) ? hs : 0.0);   // to lane r - 2
+    double cu = r < 2 ? 0.5 : ((r >= 4 && r < 8) ? hs : 0.0);                 // to lane r + 2
+    double iOm = 1.0 / Om;
+    const double one = 1.0;
+    bool have = false;                       // the LDS rows belong to every row's last key
+    double nu = (r == 0 || r == 4) ? 1.0 : 0.0;
+    double g[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int s0 = ((n_seg - 1) / 16) * 16; s0 >= 0; s0 -= 16) {
+      double Ka, Kd, Kt, Pc, Ps;
+      load_chunk(s0, Ka, Kd, Kt, Pc, Ps);
+      const int cnt = min(16, n_seg - s0);
+      for (int k = cnt; k < 16; ++k) {
+        Ka = row_ror1(Ka);
+        Kd = row_ror1(Kd);
+        Kt = row_ror1(Kt);
+        Pc = row_ror1(Pc);
+        Ps = row_ror1(Ps);
+      }
+      for (int j = cnt - 1; j >= 0; --j) {
+        const double a = row_bcast<15>(Ka), dl = row_bcast<15>(Kd), dt = row_bcast<15>(Kt);
+        const bool skip = !(dt > 0.0);
+        const bool dead = !valid || dt < 0.0;          // no derivative at all: invalid point, capped segment
+        const bool need = !skip && !(have && a == La && dl == Ld && dt == Lt);
+        if (__builtin_amdgcn_ballot_w64(need) != 0) {
+          // Every row rebuilds, a row that does not need to with its last key.  The build is the
+          // kernel's register peak, so the walk's state waits in the derivative rows, which the
+          // build replaces (the fence keeps the reads after the build).
+          double* const park[18] = {&w, &nu, &g[0], &g[1], &g[2], &g[3], &Ka, &Kd, &Kt, &Pc, &Ps, &cp, &sp,
+                                    &kqd, &e0, &cl, &cu, &iOm};
+#pragma unroll
+          for (int m = 0; m < 18; ++m) Drow[m][l] = *park[m];
+          wave_sync();
+          La = need ? a : La;
+          Ld = need ? dl : Ld;
+          Lt = need ? dt : Lt;
+          KetBlocks K;
+          KetEig E2, E3;
+          ket_blocks_build_ctl(K, E2, E3, La, Ld, Lt, d1, V);
+          ket_sched_row(K, r, u);
+          wave_sync();
+#pragma unroll
+          for (int m = 0; m < 18; ++m) *park[m] = Drow[m][l];
+          // the lane's row of each block's derivative (zeros off its block), laid out as u
+          const int e = r >> 1;
+          const bool im = (r & 1) != 0;
+          double t2[4], t3[6];
+          ket_ctl_row<2, 0>(E2, 0.5, e, im, t2);
+          ket_ctl_row<3, 0>(E3, hs, e - 2, im, t3);
+#pragma unroll
+          for (int m = 0; m < 4; ++m) Drow[m][l] = t2[m];
+#pragma unroll
+          for (int m = 0; m < 6; ++m) Drow[4 + m][l] = t3[m];
+          ket_ctl_row<2, 1>(E2, 0.5, e, im, t2);
+          ket_ctl_row<3, 1>(E3, hs, e - 2, im, t3);
+#pragma unroll
+          for (int m = 0; m < 4; ++m) Drow[10 + m][l] = t2[m];
+#pragma unroll
+          for (int m = 0; m < 6; ++m) Drow[14 + m][l] = t3[m];
+          have = true;
+        }
+        // the segment's own frame, committed only where the segment is applied
+        const double oc = row_bcast<15>(Pc), os = row_bcast<15>(Ps);
+        const double cs = skip ? cp : oc, ss = skip ? sp : os;
+        const KetSchedStep fw = ket_sched_step(cp, sp, oc, os);
+        const KetSchedStep bw = {fw.cd, -fw.sd, fw.c2, -fw.s2};
+        const double wr = ket_sched_rotate(w, kq, sg, fw), nr = ket_sched_rotate(nu, kq, sg, bw);
+        double uc[10];
+#pragma unroll
+        for (int m = 0; m < 10; ++m) uc[m] = ((m ^ r) & 1) ? -u[m] : u[m];
+        const double wn = ket_sched_apply(uc, wr);
+        const double nn = ket_sched_apply(u, nr);
+        double gn[4];
+        ket_sched_g(nn, wn, gn);
+        const double snr = sg * nr;
+        // duration: y = H_r w_s
+        double X[4];
+        {
+          const double y = fma(fma(-dl, kqd, e0), wr, a * fma(cl, row_ror2(wr), cu * row_rol2(wr)));
+          ket_ctl_sums(snr * y, nr * quad_swap(y), one, X);
+        }
+        // amplitude and detuning: y = (dU'/dtheta) w_{s-1}
+        double A[4], D[4];
+        {
+          double t[10];
+#pragma unroll
+          for (int m = 0; m < 10; ++m) t[m] = Drow[m][l];
+          const double ya = ket_sched_apply(t, wn);
+          ket_ctl_sums(snr * ya, nr * quad_swap(ya), one, A);
+#pragma unroll
+          for (int m = 0; m < 10; ++m) t[m] = Drow[10 + m][l];
+          const double yd = ket_sched_apply(t, wn);
+          ket_ctl_sums(snr * yd, nr * quad_swap(yd), one, D);
+        }
+        if (r == j) {                          // the lane's own segment: table order, c within
+          // -(i / Omega) (S_re + i S_im) = (S_im - i S_re) / Omega
+          Jrow[4 * RYD_SC_X + 0][l] = dead ? 0.0 : X[1] * iOm;
+          Jrow[4 * RYD_SC_X + 1][l] = dead ? 0.0 : -(X[0] * iOm);
+          Jrow[4 * RYD_SC_X + 2][l] = dead ? 0.0 : X[3] * iOm;
+          Jrow[4 * RYD_SC_X + 3][l] = dead ? 0.0 : -(X[2] * iOm);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            Jrow[4 * RYD_SC_AMP + c][l] = skip ? 0.0 : Om * A[c];
+            Jrow[4 * RYD_SC_DELTA + c][l] = skip ? 0.0 : Om * D[c];
+          }
+          // da/dphi_s = i (g_s - g_{s-1})
+          Jrow[4 * RYD_SC_PHASE + 0][l] = skip ? 0.0 : -(g[1] - gn[1]);
+          Jrow[4 * RYD_SC_PHASE + 1][l] = skip ? 0.0 : g[0] - gn[0];
+          Jrow[4 * RYD_SC_PHASE + 2][l] = skip ? 0.0 : -(g[3] - gn[3]);
+          Jrow[4 * RYD_SC_PHASE + 3][l] = skip ? 0.0 : g[2] - gn[2];
+        }
+        w = skip ? w : wn;
+        nu = skip ? nu : nn;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) g[c] = skip ? g[c] : gn[c];
+        cp = cs;
+        sp = ss;
+        Ka = row_ror1(Ka);
+        Kd = row_ror1(Kd);
+        Kt = row_ror1(Kt);
+        Pc = row_ror1(Pc);
+        Ps = row_ror1(Ps);
+      }
+      if (active && r < cnt) {               // s0 + r <= n_seg - 1: within the point's 16 n_seg
+        double* o = jac + (ip * ldj + (int64_t)s0 + r);
+#pragma unroll
+        for (int c = 0; c < 16; ++c) o[c * (int64_t)n_seg] = Jrow[c][l];
+      }
+    }
+  }
+}
+
+template <bool STATE>
+__global__ __launch_bounds__(S16_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 8))) void
+ket_sched_ctl_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, const double* __restrict__ sched,
+                     int64_t ldsc, int n_seg, double* __restrict__ st, int64_t lds, double* __restrict__ sm,
+                     int64_t ldm, double* __restrict__ jac, int64_t ldj, uint32_t* __restrict__ status) {
+  ket_sched_body<STATE, false, true>(prm, n, ldp, sched, ldsc, n_seg, st, lds, sm, ldm, jac, ldj, status);
 }
 
 template <bool STATE>

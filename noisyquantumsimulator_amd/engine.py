@@ -14,8 +14,8 @@ from __future__ import annotations
 
 import ctypes
 import os
-from dataclasses import dataclass
-from typing import Any, Dict, Optional, Sequence, Tuple
+from dataclasses import dataclass, field
+from typing import Any, Dict, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -98,6 +98,10 @@ class EngineResult:
     d2h_ms: float
     matvec_useful: float
     matvec_exec: float
+    # run_schedule_kets(jacobian="controls"): d a01 and d a11 with respect to every field of every
+    # segment, complex (n, 4, 2, n_seg), first index _native.SC.  By keyword only: positional
+    # construction, which ends with dim and phase_jacobian, stays as it was.
+    control_jacobian: Optional[np.ndarray] = field(default=None, kw_only=True)
     dim: int = 3
     # run_schedule_kets(jacobian=True): d a01 / d phi_s and d a11 / d phi_s, complex (n, 2, n_seg)
     phase_jacobian: Optional[np.ndarray] = None
@@ -247,6 +251,22 @@ def complex_jacobian(jac: Optional[np.ndarray]) -> Optional[np.ndarray]:
     return None if jac is None else jac[:, 0::2] + 1j * jac[:, 1::2]
 
 
+def complex_control_jacobian(jac: np.ndarray) -> np.ndarray:
+    """The library's control-Jacobian rows (n, 4 fields, 4, n_seg) -- per field Re, Im of d a01,
+    Re, Im of d a11 -- as the complex (n, 4, 2, n_seg) of ``EngineResult.control_jacobian``."""
+    return jac[:, :, 0::2] + 1j * jac[:, :, 1::2]
+
+
+def jacobian_mode(jacobian) -> bool:
+    """``jacobian`` of the schedule-ket calls: True / False (the phase Jacobian or none) give
+    False, "controls" gives True; anything else is a ValueError."""
+    if isinstance(jacobian, (bool, np.bool_)):
+        return False
+    if jacobian == "controls":
+        return True
+    raise ValueError(f'jacobian must be True, False or "controls", not {jacobian!r}')
+
+
 def check_coherence_dim(params: np.ndarray, dim: int) -> None:
     """The process-map coherence kernels exist for dim 3 and 4; dim 3 has no mJ channel, so
     a ``params`` with nonzero GMJ columns would have them silently ignored: refuse it."""
@@ -392,14 +412,18 @@ class Engine:
                             st.matvec_useful, st.matvec_exec, 3)
 
     def run_schedule_kets(self, params: np.ndarray, sched: np.ndarray, *, states: bool = True,
-                          jacobian: bool = False) -> EngineResult:
+                          jacobian: Union[bool, str] = False) -> EngineResult:
         """The caller's own pulse without noise, as kets (ryd_run_schedule_kets): ``sched`` as
         ``run_schedule`` takes it; the rate columns of ``params`` are checked and otherwise
         ignored.  The result is that of ``run(..., "ket")``.  With ``jacobian`` its
         ``phase_jacobian`` is the complex array (n, 2, n_seg) of d a01 / d phi_s (index 0) and
         d a11 / d phi_s (index 1), a01 = <01|psi_01>, a11 = <11|psi_11>
         (``pulse_schedules.overlaps(result.summary)``); state, summary and status do not depend on it.
-        ``states=False`` is a summary-only run."""
+        ``jacobian="controls"`` (ryd_run_schedule_kets_ctl) gives ``control_jacobian`` too, the
+        complex (n, 4, 2, n_seg) of the derivatives with respect to x_s, a_s, phi_s and delta_s
+        (first index ``_native.SC``, the table's units); ``phase_jacobian`` is then its
+        ``SC["PHASE"]`` slice.  ``states=False`` is a summary-only run."""
+        controls = jacobian_mode(jacobian)
         params = np.ascontiguousarray(params, dtype=np.float64)
         if params.shape[0] != N.NPARAM:
             raise ValueError(f"params must have shape ({N.NPARAM}, n)")
@@ -407,10 +431,20 @@ class Engine:
         desc, tab, ld = schedule_desc(params, sched)
         state = np.empty((N.STATE_WIDTH["ket"], 4 * n), dtype=np.float64) if states else None
         summ = np.empty((N.NSUMMARY, n), dtype=np.float64)
-        jac = np.empty((n, N.SC_NFIELD, desc.n_seg), dtype=np.float64) if jacobian else None
         status = np.zeros(n, dtype=np.uint32)
         st = N.Stats()
         dptr = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        if controls:
+            jac = np.empty((n, N.SC_NFIELD, 4, desc.n_seg), dtype=np.float64)
+            N.check(self.lib.ryd_run_schedule_kets_ctl(
+                self.handle, ctypes.byref(desc), dptr(params), n, n, dptr(tab), ld,
+                dptr(state) if states else None, 4 * n, dptr(summ), n, dptr(jac), 4 * N.SC_NFIELD * desc.n_seg,
+                status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(st)))
+            cj = complex_control_jacobian(jac)
+            return EngineResult("ket", n, state, summ, status, st.kernel_ms, st.h2d_ms, st.d2h_ms,
+                                st.matvec_useful, st.matvec_exec, 3,
+                                np.ascontiguousarray(cj[:, N.SC["PHASE"]]), control_jacobian=cj)
+        jac = np.empty((n, N.SC_NFIELD, desc.n_seg), dtype=np.float64) if jacobian else None
         N.check(self.lib.ryd_run_schedule_kets(
             self.handle, ctypes.byref(desc), dptr(params), n, n, dptr(tab), ld,
             dptr(state) if states else None, 4 * n, dptr(summ), n,
@@ -656,8 +690,9 @@ class ScheduleKetDeviceBatch:
     ``Engine.run_schedule_kets`` takes them."""
 
     def __init__(self, engine: Engine, params: np.ndarray, sched: np.ndarray, slot: int = 0,
-                 states: bool = True, jacobian: bool = False):
+                 states: bool = True, jacobian: Union[bool, str] = False):
         self.eng, self.slot = engine, slot
+        self.controls = jacobian_mode(jacobian)         # "controls": ryd_run_schedule_kets_ctl_device
         self.states, self.jacobian = states, jacobian   # False: no buffer, NULL is passed
         lib = engine.lib
         params = np.ascontiguousarray(params, dtype=np.float64)
@@ -666,7 +701,7 @@ class ScheduleKetDeviceBatch:
         self.n = n = params.shape[1]
         self.desc, tab, self.ld_sched = schedule_desc(params, sched)
         self.width = N.STATE_WIDTH["ket"]
-        self.ld_jac = N.SC_NFIELD * self.desc.n_seg
+        self.ld_jac = (4 if self.controls else 1) * N.SC_NFIELD * self.desc.n_seg
         self._bufs = []
 
         def alloc(nbytes):
@@ -687,7 +722,9 @@ class ScheduleKetDeviceBatch:
         """Enqueue one propagation of the whole batch; with ``timed`` wait and return the
         kernel's device time (HIP events on the launch stream)."""
         ms = ctypes.c_float(0.0)
-        N.check(self.eng.lib.ryd_run_schedule_kets_device(
+        lib = self.eng.lib
+        fn = lib.ryd_run_schedule_kets_ctl_device if self.controls else lib.ryd_run_schedule_kets_device
+        N.check(fn(
             self.eng.handle, self.slot, ctypes.byref(self.desc), self.d_params, self.n, self.n,
             self.d_sched, self.ld_sched, self.d_state, 4 * self.n, self.d_summary, self.n,
             self.d_jac, self.ld_jac, self.d_status, None, ctypes.byref(ms) if timed else None))
@@ -700,7 +737,11 @@ class ScheduleKetDeviceBatch:
         lib, h, s = self.eng.lib, self.eng.handle, self.slot
         state = np.zeros((self.width, 4 * self.n)) if self.states else None
         summ = np.zeros((N.NSUMMARY, self.n))
-        jac = np.zeros((self.n, N.SC_NFIELD, self.desc.n_seg)) if self.jacobian else None
+        jac = None
+        if self.controls:
+            jac = np.zeros((self.n, N.SC_NFIELD, 4, self.desc.n_seg))
+        elif self.jacobian:
+            jac = np.zeros((self.n, N.SC_NFIELD, self.desc.n_seg))
         status = np.zeros(self.n, dtype=np.uint32)
         if self.states:
             N.check(lib.ryd_memcpy_d2h(h, s, state.ctypes.data, self.d_state, state.nbytes))
@@ -708,6 +749,11 @@ class ScheduleKetDeviceBatch:
             N.check(lib.ryd_memcpy_d2h(h, s, jac.ctypes.data, self.d_jac, jac.nbytes))
         N.check(lib.ryd_memcpy_d2h(h, s, summ.ctypes.data, self.d_summary, summ.nbytes))
         N.check(lib.ryd_memcpy_d2h(h, s, status.ctypes.data, self.d_status, status.nbytes))
+        if self.controls:
+            cj = complex_control_jacobian(jac)
+            return EngineResult("ket", self.n, state, summ, status, 0.0, 0.0, 0.0,
+                                summ[N.S["NMV_USEFUL"]].sum(), summ[N.S["NMV_EXEC"]].sum(), 3,
+                                np.ascontiguousarray(cj[:, N.SC["PHASE"]]), control_jacobian=cj)
         return EngineResult("ket", self.n, state, summ, status, 0.0, 0.0, 0.0,
                             summ[N.S["NMV_USEFUL"]].sum(), summ[N.S["NMV_EXEC"]].sum(), 3, complex_jacobian(jac))
 

@@ -132,7 +132,9 @@ def gate_fidelity_and_gradient(a01: np.ndarray, a11: np.ndarray, J: np.ndarray, 
     overlaps a01 = <01|psi_01> (= <10|psi_10>) and a11 = <11|psi_11> (complex, shape (n,)), and
     its derivative with respect to every segment's phase from ``J`` (complex (n, 2, n_seg),
     ``EngineResult.phase_jacobian``: d a01 / d phi_s, d a11 / d phi_s).  ``which``: "process"
-    or "avg_gate".  Returns (F (n,), dF/dphi (n, n_seg)).
+    or "avg_gate".  Returns (F (n,), dF/dphi (n, n_seg)).  ``J`` of shape (n, 4, 2, n_seg)
+    (``EngineResult.control_jacobian``) gives dF (n, 4, n_seg) with respect to every field of the
+    table, indexed by ``SC``.
 
     With the local-Z phases (alpha, beta) that ``cz_phase_fit`` returns,
     T = 1 + a01 (e^{-i beta} + e^{-i alpha}) - a11 e^{-i (alpha + beta)}, F_pro = |T|^2 / 16,
@@ -146,8 +148,15 @@ def gate_fidelity_and_gradient(a01: np.ndarray, a11: np.ndarray, J: np.ndarray, 
     a11 = np.atleast_1d(np.asarray(a11, dtype=np.complex128))
     J = np.asarray(J, dtype=np.complex128)
     n = a01.shape[0]
+    if J.ndim == 4:                              # every field: each one as the phase alone, stacked
+        if a11.shape != (n,) or J.shape[:3] != (n, SC_NFIELD, 2):
+            raise ValueError(f"need a01 (n,), a11 (n,) and J (n, 4, 2, n_seg), got {a01.shape}, {a11.shape}, "
+                             f"{J.shape}")
+        parts = [gate_fidelity_and_gradient(a01, a11, J[:, f], which) for f in range(SC_NFIELD)]
+        return parts[0][0], np.stack([dF for _, dF in parts], axis=1)
     if a11.shape != (n,) or J.ndim != 3 or J.shape[:2] != (n, 2):
-        raise ValueError(f"need a01 (n,), a11 (n,) and J (n, 2, n_seg), got {a01.shape}, {a11.shape}, {J.shape}")
+        raise ValueError(f"need a01 (n,), a11 (n,) and J (n, 2, n_seg) or (n, 4, 2, n_seg), got {a01.shape}, "
+                         f"{a11.shape}, {J.shape}")
     # the qubit block of the four output kets: only the diagonal amplitudes are in it
     psi = np.zeros((n, 4, 9), dtype=np.complex128)
     psi[:, 0, 0] = 1.0
@@ -220,5 +229,84 @@ def optimize_phases(params: np.ndarray, sched0: np.ndarray, *, which: str = "avg
     x = np.ascontiguousarray(res.x, dtype=np.float64)
     tab[:, SC["PHASE"], :] = x.reshape(n, n_seg)
     F_final = seen[hashlib.sha1(x.tobytes()).digest()]
+    return dict(sched=tab, F_start=first[0], F_final=F_final, nfev=int(res.nfev), engine_calls=calls[0],
+                nit=int(res.nit), success=bool(res.success), message=str(res.message))
+
+
+FIELDS = {"x": SC["X"], "amp": SC["AMP"], "phase": SC["PHASE"], "delta": SC["DELTA"]}
+
+
+def optimize_schedule(params: np.ndarray, sched0: np.ndarray, *, free: Sequence[str] = ("phase",),
+                      amp_max: Optional[float] = None, duration_weight: float = 0.0, which: str = "avg_gate",
+                      maxiter: int = 200, engine=None) -> dict:
+    """Optimise chosen fields of noise-free schedules by L-BFGS-B on exact gradients.
+
+    ``optimize_phases`` with the moving fields chosen: ``free`` names them, any of "x", "amp",
+    "phase", "delta" (``FIELDS``), and the other fields stay as ``sched0`` has them.  The bounds
+    are x >= 0 and 0 <= a <= ``amp_max`` (None: no upper bound); phase and detuning are free.
+    The objective is sum_points (1 - F) + ``duration_weight`` sum_points sum_s x_s, so a positive
+    weight with "x" free trades fidelity against pulse length.  As in ``optimize_phases`` the
+    starts are one problem, and every function evaluation is exactly one
+    ``Engine.run_schedule_kets(..., states=False, jacobian="controls")`` call for all of them.
+
+    Returns the dict of ``optimize_phases``: ``sched``, ``F_start``, ``F_final`` (the fidelity
+    ``which``, without the duration term), ``nfev``, ``engine_calls``, ``nit``, ``success``,
+    ``message``."""
+    import hashlib
+
+    from scipy.optimize import minimize
+
+    from . import engine as E
+    free = tuple(free)
+    if not free or len(set(free)) != len(free) or any(f not in FIELDS for f in free):
+        raise ValueError(f"free must name distinct fields out of {tuple(FIELDS)}, not {free!r}")
+    if which not in ("process", "avg_gate"):
+        raise ValueError(f'which must be "process" or "avg_gate", not {which!r}')
+    if amp_max is not None and not (np.isfinite(amp_max) and amp_max > 0):
+        raise ValueError(f"amp_max must be a positive number or None, not {amp_max!r}")
+    if not (np.isfinite(duration_weight) and duration_weight >= 0):
+        raise ValueError(f"duration_weight must be >= 0, not {duration_weight!r}")
+    params = np.ascontiguousarray(params, dtype=np.float64)
+    n = params.shape[1]
+    tab = validate_schedule(sched0, n if np.ndim(sched0) == 3 else None)
+    if tab.ndim == 2:
+        tab = np.ascontiguousarray(np.broadcast_to(tab, (n,) + tab.shape))
+    tab = tab.copy()
+    if "amp" in free and amp_max is not None and np.any(tab[:, SC["AMP"]] > amp_max):
+        raise ValueError("sched0 has amplitudes above amp_max")
+    n_seg = tab.shape[-1]
+    idx = [FIELDS[f] for f in free]
+    lo = {"x": 0.0, "amp": 0.0}
+    hi = {"amp": amp_max}
+    bounds = [(lo.get(f), hi.get(f)) for f in free for _ in range(n * n_seg)]
+    eng = engine if engine is not None else E.Engine()
+    calls = [0]
+    seen = {}                                    # digest of an evaluated vector -> its F (n,)
+    first = []
+
+    def put(v):
+        tab[:, idx, :] = v.reshape(len(idx), n, n_seg).transpose(1, 0, 2)
+
+    def fun(v):
+        put(v)
+        r = eng.run_schedule_kets(params, tab, states=False, jacobian="controls")
+        calls[0] += 1
+        a01, a11 = overlaps(r.summary)
+        F, dF = gate_fidelity_and_gradient(a01, a11, r.control_jacobian, which)
+        if not first:
+            first.append(F)
+        seen[hashlib.sha1(v.tobytes()).digest()] = F
+        grad = -dF[:, idx, :]
+        if "x" in free:
+            grad[:, free.index("x"), :] += duration_weight
+        cost = float(np.sum(1.0 - F)) + duration_weight * float(np.sum(tab[:, SC["X"], :]))
+        return cost, np.ascontiguousarray(grad.transpose(1, 0, 2)).reshape(-1)
+
+    v0 = np.ascontiguousarray(tab[:, idx, :].transpose(1, 0, 2)).reshape(-1)
+    res = minimize(fun, v0, jac=True, method="L-BFGS-B", bounds=bounds, options=dict(maxiter=maxiter))
+    # the returned point is one of those evaluated: its F needs no further engine call
+    v = np.ascontiguousarray(res.x, dtype=np.float64)
+    put(v)
+    F_final = seen[hashlib.sha1(v.tobytes()).digest()]
     return dict(sched=tab, F_start=first[0], F_final=F_final, nfev=int(res.nfev), engine_calls=calls[0],
                 nit=int(res.nit), success=bool(res.success), message=str(res.message))
