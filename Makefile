@@ -30,7 +30,18 @@ check-dpp: asm
 kernel-diff: $(SO)
 	python3 tools/kernel_diff.py $(BASE) $(SO)
 
+# the refusals of the host-form schedule entry points under AddressSanitizer and UBSan: host code
+# only is instrumented, the program is stand-alone and needs no GPU
+HOST_REFUSALS ?= build/ryd_host_refusals
+
+host-refusals: $(SRC) tools/host_refusals.cpp
+	mkdir -p $(dir $(HOST_REFUSALS))
+	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -Wall -Wno-unused-function -ffp-contract=fast \
+	  -munsafe-fp-atomics -Xarch_host -fsanitize=address,undefined -o $(HOST_REFUSALS) $(SRC) \
+	  tools/host_refusals.cpp -ldl
+	$(HOST_REFUSALS)
+
 clean:
 	rm -f $(SO)
 
-.PHONY: all clean resource-usage asm check-dpp kernel-diff
+.PHONY: all clean resource-usage asm check-dpp kernel-diff host-refusals

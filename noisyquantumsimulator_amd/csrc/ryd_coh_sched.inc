@@ -1,7 +1,8 @@
 // ryd_coh_sched.inc -- the process-map coherences of a custom pulse schedule
-// (included by ryd_engine.hip after ryd_coh_prop.inc and ryd_sched16.inc, whose building blocks
-// it takes unchanged: cp_cheb, cp_apply0, cp_square_row / cp_square_bank, cp_frame_at, make_gen /
-// make_cgen, the Gershgorin bound, CP_XS, X_CAP; sched16_load, sched16_point_valid, row_rol1).
+// (included by ryd_engine.hip after ryd_coh_prop.inc and ryd_sched_table.inc, whose building
+// blocks it takes unchanged: cp_cheb, cp_apply0, cp_square_row / cp_square_bank, cp_frame_at,
+// make_gen / make_cgen, the Gershgorin bound, CP_XS, X_CAP; SCHED_TABLE_VALID, SCHED_CHUNK_*,
+// sched16_point_valid).  The last user of those macros: it drops them at its end.
 //
 // ryd_run_schedule_coherences[_device]: coherence_prop_kernel with the segments read from the
 // caller's table instead of segment<PROTO>().  Lindblad, dim 3, identical atoms.
@@ -15,14 +16,9 @@
 // fused loop would carry the other group's inputs, frame and key through that build.  The
 // second pass reads the table again: L2 hits, 32 bytes per segment and point.
 //
-// Table.  Read exactly as lindblad_sched16_kernel reads it: point-major
-// sched[i ld + f n_seg + s] (shared: ld = 0), in chunks of 16 segments, lane r of a row loading
-// segment s0 + r of each field, clamped to n_seg - 1; a row past the batch reads point n - 1.
-// The largest index formed is (n - 1) ld + 4 n_seg - 1.  Each lane forms its segment's key
-// (a Omega, delta Omega, x / Omega) and the (cos, sin) of its phase with fast_sincos -- the
+// Table.  Read by the protocol of ryd_sched_table.inc, with fast_sincos for the phase -- the
 // function, and therefore the frame, of the state kernel, so that the states of
-// ryd_run_schedule and these coherences join into one map.  Segment s0 + j is taken from lane 0
-// of the row after j one-lane rotations.  All address arithmetic is 64-bit.
+// ryd_run_schedule and these coherences join into one map.
 //
 // Memo.  A sector's propagator exp(L(phase 0) dt) depends on the key and the point's scalars
 // only.  It is rebuilt when the segment's key differs (==, on the three products) from the key
@@ -38,9 +34,8 @@
 // the inputs are carried into the frame of the table's phi_s as the state kernel carries its
 // states.
 //
-// Validity.  The pass and conditions of lindblad_sched16_kernel: sched16_point_valid on the
-// point's scalars, every table entry finite, x >= 0, a >= 0.  An invalid row takes part in no
-// segment and no build and writes the untouched inputs' images, E(|a><b|) = |a><b|, flagged
+// Validity.  The pass of ryd_sched_table.inc.  An invalid row takes part in no segment and no
+// build and writes the untouched inputs' images, E(|a><b|) = |a><b|, flagged
 // BAD_INPUT (as coherence_prop_kernel does for a refused point).
 //
 // Step cap.  A build whose argument (the Gershgorin width plus the rates, times dt) exceeds X_CAP
@@ -82,18 +77,9 @@ __device__ __forceinline__ void cs_sector(const double* prm, int64_t ldp, bool v
       const double* pp = prm;
       asm volatile("" : "+s"(pp));               // re-read (a cache hit), not kept live through the builds
       const double Om = pp[(int64_t)RYD_P_OMEGA * ldp + i];
-      const double x = sched16_load(tab, RYD_SC_X, n_seg, s0, l);
-      const double a = sched16_load(tab, RYD_SC_AMP, n_seg, s0, l);
-      const double ph = sched16_load(tab, RYD_SC_PHASE, n_seg, s0, l);
-      const double d = sched16_load(tab, RYD_SC_DELTA, n_seg, s0, l);
-      Ka = a * Om;
-      Kd = d * Om;
-      Kt = x / Om;
-      fast_sincos(ph, Ps, Pc);
-      if (!valid) {                              // an invalid row takes part in nothing
-        Ka = Kd = Kt = 0.0;
-        Pc = 1.0;
-        Ps = 0.0;
+      SCHED_CHUNK_LOAD(tab, n_seg, s0, l, Om)
+      if (!valid) {
+        SCHED_CHUNK_NEUTRAL()
       }
     }
     const int cnt = min(16, n_seg - s0);
@@ -252,11 +238,7 @@ __device__ __forceinline__ void cs_sector(const double* prm, int64_t ldp, bool v
           for (int s = 0; s < NIN; ++s) u[s] = acc[s];
         }
       }
-      Ka = row_rol1(Ka);
-      Kd = row_rol1(Kd);
-      Kt = row_rol1(Kt);
-      Pc = row_rol1(Pc);
-      Ps = row_rol1(Ps);
+      SCHED_CHUNK_ROL1()
     }
   }
   // ---- back to the lab frame: v = R_phi u; the qubit images ----
@@ -322,19 +304,7 @@ coherence_sched_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, c
     const PointP q = load_point<RYD_PROTO_LP_SQUARE>(prm, ldp, i);
     valid = live && sched16_point_valid(q);
   }
-  // ---- the table's validity, one pass: lane l checks segments l, l + 16, ...
-  {
-    bool ok = true;
-    for (int s0 = 0; s0 < n_seg; s0 += 16) {
-      const double x = sched16_load(tab, RYD_SC_X, n_seg, s0, l);
-      const double a = sched16_load(tab, RYD_SC_AMP, n_seg, s0, l);
-      const double ph = sched16_load(tab, RYD_SC_PHASE, n_seg, s0, l);
-      const double d = sched16_load(tab, RYD_SC_DELTA, n_seg, s0, l);
-      ok = ok && x >= 0.0 && a >= 0.0 && isfinite(x) && isfinite(a) && isfinite(ph) && isfinite(d);
-    }
-    const uint64_t bad = __builtin_amdgcn_ballot_w64(!ok);
-    valid = valid && ((bad >> (16 * row)) & 0xFFFFull) == 0;
-  }
+  SCHED_TABLE_VALID(valid, tab, n_seg, l, row)
   uint32_t stat = 0u;
   cs_sector<0>(prm, ldp, valid, tab, n_seg, l, s_U[row], s_stg[row], zl, s_park[row], out, ldo, i, live, stat);
   cs_sector<2>(prm, ldp, valid, tab, n_seg, l, s_U[row], s_stg[row], zl, s_park[row], out, ldo, i, live, stat);
@@ -345,3 +315,10 @@ coherence_sched_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, c
   if (live && !valid) st |= RYD_STATUS_BAD_INPUT;
   if (live && l == 0) status[i] = st;
 }
+
+#undef SCHED_TABLE_VALID
+#undef SCHED_CHUNK_LOAD
+#undef SCHED_CHUNK_NEUTRAL
+#undef SCHED_CHUNK_ROL1
+#undef SCHED_CHUNK_ROR1
+#undef SCHED_CHUNK_TO_LANE15

@@ -814,8 +814,49 @@ __device__ __forceinline__ void jacobi_rot(double (&A)[3][3], double (&Q)[3][3],
   }
 }
 
-__device__ __forceinline__ void ket_blocks_build(KetBlocks& B, double a, double dl, double dt, double d1,
-                                                 double V) {
+// sin h / h; below the switch its series, whose next term is h^6 / 5040 < 2e-22
+constexpr double KET_SINC_SWITCH = 1e-3;
+__device__ __forceinline__ double ket_sinc(double h) {
+  const double h2 = h * h;
+  const double ser = fma(h2, fma(h2, 1.0 / 120.0, -1.0 / 6.0), 1.0);
+  return fabs(h) < KET_SINC_SWITCH ? ser : sin(h) / h;
+}
+
+// The eigen data of one N x N block (the upper left of Q): H_r = Q diag(lambda) Q^T, and Phi's
+// upper triangle in KetBlocks' order (00 01 [02] 11 [12 22])
+struct KetEig {
+  double Q[3][3];
+  double P[6][2];
+};
+
+// Phi from the eigenvalues; (er, ei)_k = e^{-i lambda_k dt}
+template <int N>
+__device__ __forceinline__ void ket_ctl_phi(KetEig& E, const double (&lam)[3], const double (&er)[3],
+                                            const double (&ei)[3], double dt) {
+  int e = 0;
+#pragma unroll
+  for (int k = 0; k < N; ++k)
+#pragma unroll
+    for (int l = k; l < N; ++l, ++e) {
+      if (k == l) {
+        E.P[e][0] = dt * ei[k];
+        E.P[e][1] = -dt * er[k];
+      } else {
+        double sn, cs;
+        sincos(0.5 * (lam[k] + lam[l]) * dt, &sn, &cs);
+        const double sc = dt * ket_sinc(0.5 * (lam[k] - lam[l]) * dt);
+        E.P[e][0] = -sc * sn;
+        E.P[e][1] = -sc * cs;
+      }
+    }
+}
+
+// EIG: beside the propagator the eigen data of both blocks (the control Jacobian of
+// ryd_ket_sched.inc); B has the same bits either way.  The 2 x 2 block's eigenvectors come from
+// one Jacobi rotation, exact for a 2 x 2 matrix.
+template <bool EIG = false>
+__device__ __forceinline__ void ket_blocks_build(KetBlocks& B, double a, double dl, double dt, double d1, double V,
+                                                 KetEig* E2 = nullptr, KetEig* E3 = nullptr) {
   B.a = a;
   B.dl = dl;
   B.dt = dt;
@@ -834,12 +875,37 @@ __device__ __forceinline__ void ket_blocks_build(KetBlocks& B, double a, double 
       B.u2[k][0] = fma(cc, m[k][0], sc * m[k][1]);
       B.u2[k][1] = fma(cc, m[k][1], -sc * m[k][0]);
     }
+    if constexpr (EIG) {
+      double A[3][3] = {{d1, w, 0.0}, {w, -dl, 0.0}, {0.0, 0.0, 0.0}};
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) E2->Q[i][j] = i == j ? 1.0 : 0.0;
+      jacobi_rot(A, E2->Q, 0, 1);
+      const double lam[3] = {A[0][0], A[1][1], 0.0};
+      double er[3] = {1.0, 1.0, 1.0}, ei[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        double sn, cs;
+        sincos(lam[k] * dt, &sn, &cs);
+        er[k] = cs;
+        ei[k] = -sn;
+      }
+      ket_ctl_phi<2>(*E2, lam, er, ei, dt);
+    }
   }
   // 3 x 3 symmetric block: Jacobi (fixed 6 sweeps: quadratic convergence, exact zeros stop)
   {
     const double g = a * 0.70710678118654752440;     // a / sqrt2
     double A[3][3] = {{2.0 * d1, g, 0.0}, {g, d1 - dl, g}, {0.0, g, V - 2.0 * dl}};
-    double Q[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    double Ql[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    double (&Q)[3][3] = EIG ? E3->Q : Ql;
+    if constexpr (EIG) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) Q[i][j] = i == j ? 1.0 : 0.0;
+    }
 #pragma unroll 1
     for (int sweep = 0; sweep < 6; ++sweep) {
       jacobi_rot(A, Q, 0, 1);
@@ -866,6 +932,10 @@ __device__ __forceinline__ void ket_blocks_build(KetBlocks& B, double a, double 
       }
       B.u3[e][0] = re;
       B.u3[e][1] = im;
+    }
+    if constexpr (EIG) {
+      const double lam[3] = {A[0][0], A[1][1], A[2][2]};
+      ket_ctl_phi<3>(*E3, lam, er, ei, dt);
     }
   }
 }
@@ -1728,7 +1798,8 @@ __global__ __launch_bounds__(BLOCK, OCC) void jp_frame_kernel(
 #define RYD_LP_UNSQUARED 2                   // LP square, identical atoms: squaring levels left to the states
 #endif
 #include "ryd_sym16.inc"
-// custom pulse schedules on the same row layout (ryd_run_schedule)
+// custom pulse schedules on the same row layout: the table reader, then ryd_run_schedule
+#include "ryd_sched_table.inc"
 #include "ryd_sched16.inc"
 // the same tables as kets, with the overlaps' phase gradients (ryd_run_schedule_kets)
 #include "ryd_ket_sched.inc"
@@ -2611,21 +2682,27 @@ int validate_schedule(const ryd_sched_desc* d, const double* sched, int64_t n, i
   return RYD_OK;
 }
 
-// One schedule batch on `stream` (ryd_sched16.inc); ds = NULL takes the store-free twin.  The
-// kernel addresses a shared table as a per-point one of leading dimension 0.
+// What the schedule launches share: nothing to do for n = 0, and `go(ld, n_seg, grid)` with the
+// table's leading dimension as the kernels take it (a shared table is a per-point one of
+// leading dimension 0) and the grid of `per_block` points per block.
+template <typename Go>
+int launch_sched(const ryd_sched_desc* d, int64_t n, int64_t ldsc, int per_block, Go&& go) {
+  if (n == 0) return RYD_OK;
+  return go((d->flags & RYD_SCHED_SHARED) ? (int64_t)0 : ldsc, (int)d->n_seg, (n + per_block - 1) / per_block);
+}
+
+// One schedule batch on `stream` (ryd_sched16.inc); ds = NULL takes the store-free twin.
 int launch_schedule(const ryd_sched_desc* d, const double* dp, int64_t n, int64_t ldp, const double* dsc,
                     int64_t ldsc, double* ds, int64_t lds, double* dm, int64_t ldm, uint32_t* dstat,
                     hipStream_t stream) {
-  if (n == 0) return RYD_OK;
   if (!ds) lds = 0;
   // the output stores' 32-bit lane offsets, as launch_sym16 checks them
   const int st32 = sym16_store32_enabled() && lds >= 0 && ldm >= 0 && lds <= (0x1fffffffLL - 15) / 3 &&
                    ldm <= (0x1fffffffLL - 3) / 15;
-  const int64_t ld = (d->flags & RYD_SCHED_SHARED) ? 0 : ldsc;
-  const int nseg = d->n_seg;
-  return launch_typed(ds ? lindblad_sched16_kernel<true> : lindblad_sched16_kernel<false>,
-                      (n + S16_PPW - 1) / S16_PPW, S16_BLOCK, 0, stream, dp, n, ldp, dsc, ld, nseg, ds, lds, dm, ldm,
-                      dstat, st32);
+  return launch_sched(d, n, ldsc, S16_PPW, [&](int64_t ld, int nseg, int64_t grid) {
+    return launch_typed(ds ? lindblad_sched16_kernel<true> : lindblad_sched16_kernel<false>, grid, S16_BLOCK, 0,
+                        stream, dp, n, ldp, dsc, ld, nseg, ds, lds, dm, ldm, dstat, st32);
+  });
 }
 
 // ryd_run_schedule_kets[_device]: validate_schedule's rules (the descriptor first), then the
@@ -2638,20 +2715,22 @@ int validate_schedule_kets(const ryd_sched_desc* d, const double* sched, int64_t
 }
 
 // One noise-free schedule batch as kets on `stream` (ryd_ket_sched.inc); ds = NULL takes the
-// store-free twin, dj = NULL the forward kernel alone.
-int launch_schedule_kets(const ryd_sched_desc* d, const double* dp, int64_t n, int64_t ldp, const double* dsc,
-                         int64_t ldsc, double* ds, int64_t lds, double* dm, int64_t ldm, double* dj, int64_t ldj,
-                         uint32_t* dstat, hipStream_t stream) {
-  if (n == 0) return RYD_OK;
+// store-free twin.  ctl: the Jacobian of all four fields (ket_sched_ctl_kernel); else dj = NULL
+// takes the forward kernel alone.
+int launch_schedule_kets(bool ctl, const ryd_sched_desc* d, const double* dp, int64_t n, int64_t ldp,
+                         const double* dsc, int64_t ldsc, double* ds, int64_t lds, double* dm, int64_t ldm,
+                         double* dj, int64_t ldj, uint32_t* dstat, hipStream_t stream) {
   if (!ds) lds = 0;
-  const int64_t ld = (d->flags & RYD_SCHED_SHARED) ? 0 : ldsc;
-  const int nseg = d->n_seg;
-  const int64_t grid = (n + S16_PPW - 1) / S16_PPW;
-  if (dj)
-    return launch_typed(ds ? ket_sched_jac_kernel<true> : ket_sched_jac_kernel<false>, grid, S16_BLOCK, 0, stream, dp,
-                        n, ldp, dsc, ld, nseg, ds, lds, dm, ldm, dj, ldj, dstat);
-  return launch_typed(ds ? ket_sched_kernel<true> : ket_sched_kernel<false>, grid, S16_BLOCK, 0, stream, dp, n, ldp,
-                      dsc, ld, nseg, ds, lds, dm, ldm, dstat);
+  return launch_sched(d, n, ldsc, S16_PPW, [&](int64_t ld, int nseg, int64_t grid) {
+    if (ctl)
+      return launch_typed(ds ? ket_sched_ctl_kernel<true> : ket_sched_ctl_kernel<false>, grid, S16_BLOCK, 0, stream,
+                          dp, n, ldp, dsc, ld, nseg, ds, lds, dm, ldm, dj, ldj, dstat);
+    if (dj)
+      return launch_typed(ds ? ket_sched_jac_kernel<true> : ket_sched_jac_kernel<false>, grid, S16_BLOCK, 0, stream,
+                          dp, n, ldp, dsc, ld, nseg, ds, lds, dm, ldm, dj, ldj, dstat);
+    return launch_typed(ds ? ket_sched_kernel<true> : ket_sched_kernel<false>, grid, S16_BLOCK, 0, stream, dp, n, ldp,
+                        dsc, ld, nseg, ds, lds, dm, ldm, dstat);
+  });
 }
 
 // ryd_run_schedule_kets_ctl[_device]: validate_schedule_kets' rules, with the Jacobian required
@@ -2662,18 +2741,6 @@ int validate_schedule_kets_ctl(const ryd_sched_desc* d, const double* sched, int
   if (!jac) return fail(RYD_ERR_INVALID, "the control Jacobian is NULL");
   if (ldj < 4 * (int64_t)RYD_SC_NFIELD * d->n_seg) return fail(RYD_ERR_INVALID, "ld_jac is smaller than 16 n_seg");
   return RYD_OK;
-}
-
-// One noise-free schedule batch with the Jacobian of all four fields (ket_sched_ctl_kernel)
-int launch_schedule_kets_ctl(const ryd_sched_desc* d, const double* dp, int64_t n, int64_t ldp, const double* dsc,
-                             int64_t ldsc, double* ds, int64_t lds, double* dm, int64_t ldm, double* dj, int64_t ldj,
-                             uint32_t* dstat, hipStream_t stream) {
-  if (n == 0) return RYD_OK;
-  if (!ds) lds = 0;
-  const int64_t ld = (d->flags & RYD_SCHED_SHARED) ? 0 : ldsc;
-  const int nseg = d->n_seg;
-  return launch_typed(ds ? ket_sched_ctl_kernel<true> : ket_sched_ctl_kernel<false>, (n + S16_PPW - 1) / S16_PPW,
-                      S16_BLOCK, 0, stream, dp, n, ldp, dsc, ld, nseg, ds, lds, dm, ldm, dj, ldj, dstat);
 }
 
 // RYD_COH_PROP=0 selects coherence_cheb_kernel for every protocol (A/B and cross-check runs)
@@ -2709,16 +2776,14 @@ int validate_schedule_coherences(const ryd_sched_desc* d, const double* sched, i
 }
 
 // The coherence sectors of one schedule batch (ryd_coh_sched.inc, one launch); status is cleared
-// first, as launch_coherences does.  A shared table is a per-point one of leading dimension 0.
+// first, as launch_coherences does.
 int launch_schedule_coherences(const ryd_sched_desc* d, const double* dp, int64_t n, int64_t ldp,
                                const double* dsc, int64_t ldsc, double* dc, int64_t ldc, uint32_t* dstat,
                                hipStream_t stream) {
-  if (n == 0) return RYD_OK;
-  HIPCHK(hipMemsetAsync(dstat, 0, sizeof(uint32_t) * n, stream));
-  const int64_t ld = (d->flags & RYD_SCHED_SHARED) ? 0 : ldsc;
-  const int nseg = d->n_seg;
-  return launch_typed(coherence_sched_kernel, (n + CP_NR - 1) / CP_NR, CP_BLOCK, 0, stream, dp, n, ldp, dsc, ld,
-                      nseg, dc, ldc, dstat);
+  return launch_sched(d, n, ldsc, CP_NR, [&](int64_t ld, int nseg, int64_t grid) {
+    HIPCHK(hipMemsetAsync(dstat, 0, sizeof(uint32_t) * n, stream));
+    return launch_typed(coherence_sched_kernel, grid, CP_BLOCK, 0, stream, dp, n, ldp, dsc, ld, nseg, dc, ldc, dstat);
+  });
 }
 
 int validate_coherences(const ryd_batch_desc* d, int64_t n, int64_t ldp, int64_t ldc) {
@@ -3163,6 +3228,66 @@ int run_partitioned(ryd_handle* h, const double* params, int64_t n, int64_t ld_p
   return RYD_OK;
 }
 
+// The host-form entry points after their own validation: the handle and NULL checks (the last
+// array of `outs` is the one every call requires: the summary, or the coherence rows),
+// run_partitioned with the optional second input `tab`, and the stats.  counts: the last array
+// is a summary whose iteration rows the stats sum.  The launch callable gets the slot's points
+// and its device arrays in the order of `outs`: go(dp, cnt, ldp, o, dstat, stream).
+template <typename Go>
+int run_host(ryd_handle* h, const double* params, int64_t n, int64_t ld_params, const std::vector<HostOut>& outs,
+             HostIn* tab, uint32_t* out_status, ryd_stats* stats, bool counts, Go&& go) {
+  if (!h) return fail(RYD_ERR_INVALID, "handle is NULL");
+  const HostOut& req = outs.back();
+  if (n > 0 && (!params || !req.host || !out_status)) return fail(RYD_ERR_INVALID, "NULL buffer");
+  double kms, hms, dms;
+  int rc = run_partitioned(
+      h, params, n, ld_params, outs, out_status,
+      [&](const double* dp, int64_t cnt, int64_t ldp, int64_t, const std::vector<double*>& o, uint32_t* dst,
+          hipStream_t s) { return go(dp, cnt, ldp, o, dst, s); },
+      kms, hms, dms, tab);
+  if (rc) return rc;
+  fill_stats(stats, h, kms, hms, dms, counts ? req.host : nullptr, req.ld, n, RYD_S_NMV_USEFUL, RYD_S_NMV_EXEC);
+  return RYD_OK;
+}
+
+// The caller's schedule table as run_partitioned's second input
+HostIn sched_table_in(const ryd_sched_desc* d, const double* sched, int64_t ld_sched) {
+  return {sched, ld_sched, (int64_t)RYD_SC_NFIELD * d->n_seg, (d->flags & RYD_SCHED_SHARED) != 0};
+}
+
+// The output list of a summary-carrying call: the state rows (out_state NULL: a summary-only
+// call, whose device workspace, staging buffer, D2H and unpack carry no state rows), a Jacobian
+// of jw doubles per point (packed on the device: its leading dimension there is jw; the caller's
+// points are ld_jac apart, as the table's are on the way in), then the summary.
+std::vector<HostOut> summary_outs(double* out_state, int64_t ld_state, int state_rows, double* out_summary,
+                                  int64_t ld_summary, double* out_jac = nullptr, int jw = 0, int64_t ld_jac = 0) {
+  std::vector<HostOut> outs;
+  if (out_state) outs.push_back({out_state, ld_state, state_rows, 4});
+  if (out_jac) outs.push_back({out_jac, 0, 1, jw, ld_jac});
+  outs.push_back({out_summary, ld_summary, RYD_NSUMMARY, 1});
+  return outs;
+}
+
+// ryd_run_schedule_kets and (ctl: the Jacobian four fields wide) ryd_run_schedule_kets_ctl after
+// validation
+int run_schedule_kets_host(bool ctl, ryd_handle* h, const ryd_sched_desc* desc, const double* params, int64_t n,
+                           int64_t ld_params, const double* sched, int64_t ld_sched, double* out_state,
+                           int64_t ld_state, double* out_summary, int64_t ld_summary, double* out_jac,
+                           int64_t ld_jac, uint32_t* out_status, ryd_stats* stats) {
+  const int jw = (ctl ? 4 : 1) * RYD_SC_NFIELD * desc->n_seg;
+  HostIn tab = sched_table_in(desc, sched, ld_sched);
+  return run_host(h, params, n, ld_params,
+                  summary_outs(out_state, ld_state, ryd_state_width(RYD_EVOL_KET, 3), out_summary, ld_summary, out_jac,
+                               jw, ld_jac),
+                  &tab, out_status, stats, true,
+                  [&](const double* dp, int64_t cnt, int64_t ldp, const std::vector<double*>& o, uint32_t* dst,
+                      hipStream_t s) {
+                    return launch_schedule_kets(ctl, desc, dp, cnt, ldp, tab.dev, ld_sched,
+                                                out_state ? o[0] : nullptr, 4 * cnt, o.back(), cnt,
+                                                out_jac ? o[out_state ? 1 : 0] : nullptr, jw, dst, s);
+                  });
+}
+
 // three-atom quantum-jump trajectories (BASELINE configs[4])
 #include "ryd_traj.inc"
 #include "ryd_generic.inc"
@@ -3347,27 +3472,14 @@ int ryd_run_batch(ryd_handle* h, const ryd_batch_desc* desc, const double* param
                   int64_t ld_params, double* out_state, int64_t ld_state, double* out_summary,
                   int64_t ld_summary, uint32_t* out_status, ryd_stats* stats) {
   if (!h) return fail(RYD_ERR_INVALID, "handle is NULL");
-  int rc = validate(desc, n, ld_params, ld_state, ld_summary, out_state != nullptr);
-  if (rc) return rc;
-  if (n > 0 && (!params || !out_summary || !out_status))
-    return fail(RYD_ERR_INVALID, "NULL buffer");
-  const int sw = ryd_state_width(desc->evolution, desc->dim);
-  // summary-only (out_state NULL): the summary is the only output array, so the device
-  // workspace, the staging buffer, the D2H and the unpack carry no state rows
-  std::vector<HostOut> outs;
-  if (out_state) outs.push_back({out_state, ld_state, sw, 4});
-  outs.push_back({out_summary, ld_summary, RYD_NSUMMARY, 1});
-  double kms, hms, dms;
-  rc = run_partitioned(
-      h, params, n, ld_params, outs, out_status,
-      [&](const double* dp, int64_t cnt, int64_t ldp, int64_t, const std::vector<double*>& o, uint32_t* dst,
-          hipStream_t s) {
-        return launch(desc, dp, cnt, ldp, out_state ? o[0] : nullptr, 4 * cnt, o.back(), cnt, dst, s);
-      },
-      kms, hms, dms);
-  if (rc) return rc;
-  fill_stats(stats, h, kms, hms, dms, out_summary, ld_summary, n, RYD_S_NMV_USEFUL, RYD_S_NMV_EXEC);
-  return RYD_OK;
+  if (int rc = validate(desc, n, ld_params, ld_state, ld_summary, out_state != nullptr)) return rc;
+  return run_host(h, params, n, ld_params,
+                  summary_outs(out_state, ld_state, ryd_state_width(desc->evolution, desc->dim), out_summary, ld_summary),
+                  nullptr, out_status, stats, true,
+                  [&](const double* dp, int64_t cnt, int64_t ldp, const std::vector<double*>& o, uint32_t* dst,
+                      hipStream_t s) {
+                    return launch(desc, dp, cnt, ldp, out_state ? o[0] : nullptr, 4 * cnt, o.back(), cnt, dst, s);
+                  });
 }
 
 int ryd_run_schedule_device(ryd_handle* h, int slot, const ryd_sched_desc* desc, const double* d_params,
@@ -3388,26 +3500,17 @@ int ryd_run_schedule(ryd_handle* h, const ryd_sched_desc* desc, const double* pa
                      int64_t ld_state, double* out_summary, int64_t ld_summary, uint32_t* out_status,
                      ryd_stats* stats) {
   // the descriptor first, so that each refusal reports its own reason with or without a handle
-  int rc = validate_schedule(desc, sched, n, ld_params, ld_sched, ld_state, ld_summary, out_state != nullptr);
-  if (rc) return rc;
-  if (!h) return fail(RYD_ERR_INVALID, "handle is NULL");
-  if (n > 0 && (!params || !out_summary || !out_status)) return fail(RYD_ERR_INVALID, "NULL buffer");
-  std::vector<HostOut> outs;
-  if (out_state) outs.push_back({out_state, ld_state, NC, 4});
-  outs.push_back({out_summary, ld_summary, RYD_NSUMMARY, 1});
-  HostIn tab = {sched, ld_sched, (int64_t)RYD_SC_NFIELD * desc->n_seg, (desc->flags & RYD_SCHED_SHARED) != 0};
-  double kms, hms, dms;
-  rc = run_partitioned(
-      h, params, n, ld_params, outs, out_status,
-      [&](const double* dp, int64_t cnt, int64_t ldp, int64_t, const std::vector<double*>& o, uint32_t* dst,
-          hipStream_t s) {
-        return launch_schedule(desc, dp, cnt, ldp, tab.dev, ld_sched, out_state ? o[0] : nullptr, 4 * cnt, o.back(),
-                               cnt, dst, s);
-      },
-      kms, hms, dms, &tab);
-  if (rc) return rc;
-  fill_stats(stats, h, kms, hms, dms, out_summary, ld_summary, n, RYD_S_NMV_USEFUL, RYD_S_NMV_EXEC);
-  return RYD_OK;
+  // (so in every host-form schedule call)
+  if (int rc = validate_schedule(desc, sched, n, ld_params, ld_sched, ld_state, ld_summary, out_state != nullptr))
+    return rc;
+  HostIn tab = sched_table_in(desc, sched, ld_sched);
+  return run_host(h, params, n, ld_params, summary_outs(out_state, ld_state, NC, out_summary, ld_summary), &tab,
+                  out_status, stats, true,
+                  [&](const double* dp, int64_t cnt, int64_t ldp, const std::vector<double*>& o, uint32_t* dst,
+                      hipStream_t s) {
+                    return launch_schedule(desc, dp, cnt, ldp, tab.dev, ld_sched, out_state ? o[0] : nullptr, 4 * cnt,
+                                           o.back(), cnt, dst, s);
+                  });
 }
 
 int ryd_run_schedule_kets_device(ryd_handle* h, int slot, const ryd_sched_desc* desc, const double* d_params,
@@ -3422,8 +3525,8 @@ int ryd_run_schedule_kets_device(ryd_handle* h, int slot, const ryd_sched_desc* 
                                       ld_jac, d_jac != nullptr);
       },
       [&](hipStream_t s) {
-        return launch_schedule_kets(desc, d_params, n, ld_params, d_sched, ld_sched, d_state, ld_state, d_summary,
-                                    ld_summary, d_jac, ld_jac, d_status, s);
+        return launch_schedule_kets(false, desc, d_params, n, ld_params, d_sched, ld_sched, d_state, ld_state,
+                                    d_summary, ld_summary, d_jac, ld_jac, d_status, s);
       });
 }
 
@@ -3431,33 +3534,11 @@ int ryd_run_schedule_kets(ryd_handle* h, const ryd_sched_desc* desc, const doubl
                           int64_t ld_params, const double* sched, int64_t ld_sched, double* out_state,
                           int64_t ld_state, double* out_summary, int64_t ld_summary, double* out_jac,
                           int64_t ld_jac, uint32_t* out_status, ryd_stats* stats) {
-  // the descriptor first, so that each refusal reports its own reason with or without a handle
-  int rc = validate_schedule_kets(desc, sched, n, ld_params, ld_sched, ld_state, ld_summary, out_state != nullptr,
-                                  ld_jac, out_jac != nullptr);
-  if (rc) return rc;
-  if (!h) return fail(RYD_ERR_INVALID, "handle is NULL");
-  if (n > 0 && (!params || !out_summary || !out_status)) return fail(RYD_ERR_INVALID, "NULL buffer");
-  // the Jacobian travels out as the table travels in: a slot's rows are one contiguous block
-  // of the caller's array (packed on the device: its leading dimension there is 4 n_seg)
-  const int jw = RYD_SC_NFIELD * desc->n_seg;
-  std::vector<HostOut> outs;
-  if (out_state) outs.push_back({out_state, ld_state, ryd_state_width(RYD_EVOL_KET, 3), 4});
-  if (out_jac) outs.push_back({out_jac, 0, 1, jw, ld_jac});
-  outs.push_back({out_summary, ld_summary, RYD_NSUMMARY, 1});
-  const int ij = out_state ? 1 : 0;
-  HostIn tab = {sched, ld_sched, (int64_t)RYD_SC_NFIELD * desc->n_seg, (desc->flags & RYD_SCHED_SHARED) != 0};
-  double kms, hms, dms;
-  rc = run_partitioned(
-      h, params, n, ld_params, outs, out_status,
-      [&](const double* dp, int64_t cnt, int64_t ldp, int64_t, const std::vector<double*>& o, uint32_t* dst,
-          hipStream_t s) {
-        return launch_schedule_kets(desc, dp, cnt, ldp, tab.dev, ld_sched, out_state ? o[0] : nullptr, 4 * cnt,
-                                    o.back(), cnt, out_jac ? o[ij] : nullptr, jw, dst, s);
-      },
-      kms, hms, dms, &tab);
-  if (rc) return rc;
-  fill_stats(stats, h, kms, hms, dms, out_summary, ld_summary, n, RYD_S_NMV_USEFUL, RYD_S_NMV_EXEC);
-  return RYD_OK;
+  if (int rc = validate_schedule_kets(desc, sched, n, ld_params, ld_sched, ld_state, ld_summary,
+                                      out_state != nullptr, ld_jac, out_jac != nullptr))
+    return rc;
+  return run_schedule_kets_host(false, h, desc, params, n, ld_params, sched, ld_sched, out_state, ld_state, out_summary,
+                                ld_summary, out_jac, ld_jac, out_status, stats);
 }
 
 int ryd_run_schedule_kets_ctl_device(ryd_handle* h, int slot, const ryd_sched_desc* desc, const double* d_params,
@@ -3472,8 +3553,8 @@ int ryd_run_schedule_kets_ctl_device(ryd_handle* h, int slot, const ryd_sched_de
                                           d_state != nullptr, d_jac, ld_jac);
       },
       [&](hipStream_t s) {
-        return launch_schedule_kets_ctl(desc, d_params, n, ld_params, d_sched, ld_sched, d_state, ld_state, d_summary,
-                                        ld_summary, d_jac, ld_jac, d_status, s);
+        return launch_schedule_kets(true, desc, d_params, n, ld_params, d_sched, ld_sched, d_state, ld_state,
+                                    d_summary, ld_summary, d_jac, ld_jac, d_status, s);
       });
 }
 
@@ -3481,73 +3562,33 @@ int ryd_run_schedule_kets_ctl(ryd_handle* h, const ryd_sched_desc* desc, const d
                               int64_t ld_params, const double* sched, int64_t ld_sched, double* out_state,
                               int64_t ld_state, double* out_summary, int64_t ld_summary, double* out_jac,
                               int64_t ld_jac, uint32_t* out_status, ryd_stats* stats) {
-  int rc = validate_schedule_kets_ctl(desc, sched, n, ld_params, ld_sched, ld_state, ld_summary,
-                                      out_state != nullptr, out_jac, ld_jac);
-  if (rc) return rc;
-  if (!h) return fail(RYD_ERR_INVALID, "handle is NULL");
-  if (n > 0 && (!params || !out_summary || !out_status)) return fail(RYD_ERR_INVALID, "NULL buffer");
-  // as ryd_run_schedule_kets, four fields wide: packed on the device, leading dimension 16 n_seg
-  const int jw = 4 * RYD_SC_NFIELD * desc->n_seg;
-  std::vector<HostOut> outs;
-  if (out_state) outs.push_back({out_state, ld_state, ryd_state_width(RYD_EVOL_KET, 3), 4});
-  outs.push_back({out_jac, 0, 1, jw, ld_jac});
-  outs.push_back({out_summary, ld_summary, RYD_NSUMMARY, 1});
-  const int ij = out_state ? 1 : 0;
-  HostIn tab = {sched, ld_sched, (int64_t)RYD_SC_NFIELD * desc->n_seg, (desc->flags & RYD_SCHED_SHARED) != 0};
-  double kms, hms, dms;
-  rc = run_partitioned(
-      h, params, n, ld_params, outs, out_status,
-      [&](const double* dp, int64_t cnt, int64_t ldp, int64_t, const std::vector<double*>& o, uint32_t* dst,
-          hipStream_t s) {
-        return launch_schedule_kets_ctl(desc, dp, cnt, ldp, tab.dev, ld_sched, out_state ? o[0] : nullptr, 4 * cnt,
-                                        o.back(), cnt, o[ij], jw, dst, s);
-      },
-      kms, hms, dms, &tab);
-  if (rc) return rc;
-  fill_stats(stats, h, kms, hms, dms, out_summary, ld_summary, n, RYD_S_NMV_USEFUL, RYD_S_NMV_EXEC);
-  return RYD_OK;
+  if (int rc = validate_schedule_kets_ctl(desc, sched, n, ld_params, ld_sched, ld_state, ld_summary,
+                                          out_state != nullptr, out_jac, ld_jac))
+    return rc;
+  return run_schedule_kets_host(true, h, desc, params, n, ld_params, sched, ld_sched, out_state, ld_state, out_summary,
+                                ld_summary, out_jac, ld_jac, out_status, stats);
 }
 
 int ryd_run_coherences(ryd_handle* h, const ryd_batch_desc* desc, const double* params, int64_t n,
                        int64_t ld_params, double* out_coh, int64_t ld_coh, uint32_t* out_status,
                        ryd_stats* stats) {
   if (!h) return fail(RYD_ERR_INVALID, "handle is NULL");
-  int rc = validate_coherences(desc, n, ld_params, ld_coh);
-  if (rc) return rc;
-  if (n > 0 && (!params || !out_coh || !out_status)) return fail(RYD_ERR_INVALID, "NULL buffer");
-  const std::vector<HostOut> outs = {{out_coh, ld_coh, RYD_NCOH, 1}};
-  double kms, hms, dms;
-  rc = run_partitioned(
-      h, params, n, ld_params, outs, out_status,
-      [&](const double* dp, int64_t cnt, int64_t ldp, int64_t, const std::vector<double*>& o, uint32_t* dst,
-          hipStream_t s) { return launch_coherences(desc, dp, cnt, ldp, o[0], cnt, dst, s); },
-      kms, hms, dms);
-  if (rc) return rc;
-  fill_stats(stats, h, kms, hms, dms, nullptr, 0, 0, 0, 0);
-  return RYD_OK;
+  if (int rc = validate_coherences(desc, n, ld_params, ld_coh)) return rc;
+  return run_host(h, params, n, ld_params, {{out_coh, ld_coh, RYD_NCOH, 1}}, nullptr, out_status, stats, false,
+                  [&](const double* dp, int64_t cnt, int64_t ldp, const std::vector<double*>& o, uint32_t* dst,
+                      hipStream_t s) { return launch_coherences(desc, dp, cnt, ldp, o[0], cnt, dst, s); });
 }
 
 int ryd_run_schedule_coherences(ryd_handle* h, const ryd_sched_desc* desc, const double* params, int64_t n,
                                 int64_t ld_params, const double* sched, int64_t ld_sched, double* out_coh,
                                 int64_t ld_coh, uint32_t* out_status, ryd_stats* stats) {
-  // the descriptor first, so that each refusal reports its own reason with or without a handle
-  int rc = validate_schedule_coherences(desc, sched, n, ld_params, ld_sched, ld_coh);
-  if (rc) return rc;
-  if (!h) return fail(RYD_ERR_INVALID, "handle is NULL");
-  if (n > 0 && (!params || !out_coh || !out_status)) return fail(RYD_ERR_INVALID, "NULL buffer");
-  const std::vector<HostOut> outs = {{out_coh, ld_coh, RYD_NCOH, 1}};
-  HostIn tab = {sched, ld_sched, (int64_t)RYD_SC_NFIELD * desc->n_seg, (desc->flags & RYD_SCHED_SHARED) != 0};
-  double kms, hms, dms;
-  rc = run_partitioned(
-      h, params, n, ld_params, outs, out_status,
-      [&](const double* dp, int64_t cnt, int64_t ldp, int64_t, const std::vector<double*>& o, uint32_t* dst,
-          hipStream_t s) {
-        return launch_schedule_coherences(desc, dp, cnt, ldp, tab.dev, ld_sched, o[0], cnt, dst, s);
-      },
-      kms, hms, dms, &tab);
-  if (rc) return rc;
-  fill_stats(stats, h, kms, hms, dms, nullptr, 0, 0, 0, 0);
-  return RYD_OK;
+  if (int rc = validate_schedule_coherences(desc, sched, n, ld_params, ld_sched, ld_coh)) return rc;
+  HostIn tab = sched_table_in(desc, sched, ld_sched);
+  return run_host(h, params, n, ld_params, {{out_coh, ld_coh, RYD_NCOH, 1}}, &tab, out_status, stats, false,
+                  [&](const double* dp, int64_t cnt, int64_t ldp, const std::vector<double*>& o, uint32_t* dst,
+                      hipStream_t s) {
+                    return launch_schedule_coherences(desc, dp, cnt, ldp, tab.dev, ld_sched, o[0], cnt, dst, s);
+                  });
 }
 
 int ryd_run_schedule_coherences_device(ryd_handle* h, int slot, const ryd_sched_desc* desc, const double* d_params,

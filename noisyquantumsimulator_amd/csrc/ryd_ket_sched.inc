@@ -1,6 +1,6 @@
 // ryd_ket_sched.inc -- noise-free custom pulse schedules as kets, with the derivatives of the
 // two diagonal overlaps with respect to every segment's phase (included by ryd_engine.hip after
-// ryd_sched16.inc, inside the anonymous namespace).
+// ryd_sched_table.inc and ryd_sched16.inc, inside the anonymous namespace).
 //
 // ryd_run_schedule_kets[_device]: the table of ryd_run_schedule (ryd_sched16.inc), dim 3,
 // identical atoms, no rates.  The layout is the family's: four points per wave, one 16-lane
@@ -12,12 +12,10 @@
 // (dot5_bcast).  The laser phase is a frame, D = diag(1, e^{i phi}[, e^{2 i phi}]), carried
 // relatively from segment to segment as lindblad_sched16_kernel carries (cp, sp).
 //
-// Table.  Read as lindblad_sched16_kernel reads it (sched16_load, chunks of 16, lane r takes
-// segment s0 + r clamped, one fast_sincos per chunk, segments taken from lane 0 after row_rol1
-// rotations, a shared table is leading dimension 0, a row past the batch reads point n - 1),
-// with the same validity pass; the rate columns take part in sched16_point_valid and in
-// nothing else.  The lane also forms its segment's step cap (h_bounds, X_CAP, as
-// ket_block_kernel) and marks a capped segment with the duration -1, which no valid table holds.
+// Table.  Read by the protocol of ryd_sched_table.inc (SCHED_TABLE_VALID, SCHED_CHUNK_*), the
+// point's Omega held in a register; the rate columns take part in sched16_point_valid and in
+// nothing else.  The lane also forms its segment's step cap (h_bounds, X_CAP, as ket_block_kernel) and
+// marks a capped segment with the duration -1, which no valid table holds.
 // A chunk whose segments all run on every row's current propagator (a phase-only stretch) takes
 // a shorter loop: the lanes form their segments' frame steps sixteen at once, and a segment is
 // four broadcasts, the rotation and the ten FMAs, with no key, compare or ballot.  Both loops do
@@ -34,9 +32,9 @@
 // b_{s-1} = U_s^{-1} b_s (the conjugate of the complex-symmetric U' in the frame),
 // lambda_{s-1} = U_s^T lambda_s (U' itself, in the conjugate frame: nu = D lambda), and
 // g = sum_k k nu_k w_k in any common frame.  The chunks and their segments are taken in
-// reverse, from lane 15 after row_ror1 rotations (a partial last chunk is rotated up first);
-// lane j keeps the four numbers of segment s0 + j, so a row stores 16 segments of a component
-// as one 128-byte piece of jac[i ld_jac + c n_seg + s], c = Re da01, Im da01, Re da11, Im da11.
+// reverse (SCHED_CHUNK_TO_LANE15, SCHED_CHUNK_ROR1); lane j keeps the four numbers of segment
+// s0 + j, so a row stores 16 segments of a component as one 128-byte piece of
+// jac[i ld_jac + c n_seg + s], c = Re da01, Im da01, Re da11, Im da11.
 // A skipped segment and every segment of an invalid point get exact zeros.
 //
 // Control Jacobian (ket_sched_ctl_kernel, ryd_run_schedule_kets_ctl).  The same forward pass
@@ -50,9 +48,6 @@
 // 168 spills 116-132 bytes per lane around ket_blocks_build, so none is set.  The control
 // kernel: 253 VGPRs, no scratch, 18,432 bytes of LDS (derivative rows, chunk results, and the
 // walk's state parked across a build), 2 waves per SIMD under amdgpu_waves_per_eu(2, 8).
-
-// lane r takes the value of lane (r - 1) mod 16 of its row: row_ror:1
-__device__ __forceinline__ double row_ror1(double v) { return dpp32x2<0x121>(v); }
 
 // Row r of the block-diagonal propagator in real form (r >= 10: zeros).
 __device__ __forceinline__ void ket_sched_row(const KetBlocks& K, int r, double (&u)[10]) {
@@ -129,43 +124,6 @@ __device__ __forceinline__ void ket_sched_g(double nu, double w, double (&g)[4])
 // finite for every gap (Phi_kk = -i dt e^{-i lambda_k dt}); H_a is the coupling pattern (cpl on
 // the off-diagonals next to the diagonal), H_Delta = -diag(0, 1[, 2]).
 
-// sin h / h; below the switch its series, whose next term is h^6 / 5040 < 2e-22
-constexpr double KET_SINC_SWITCH = 1e-3;
-__device__ __forceinline__ double ket_sinc(double h) {
-  const double h2 = h * h;
-  const double ser = fma(h2, fma(h2, 1.0 / 120.0, -1.0 / 6.0), 1.0);
-  return fabs(h) < KET_SINC_SWITCH ? ser : sin(h) / h;
-}
-
-// The eigen data of one N x N block (the upper left of Q): H_r = Q diag(lambda) Q^T, and Phi's
-// upper triangle in KetBlocks' order (00 01 [02] 11 [12 22])
-struct KetEig {
-  double Q[3][3];
-  double P[6][2];
-};
-
-// Phi from the eigenvalues; (er, ei)_k = e^{-i lambda_k dt}
-template <int N>
-__device__ __forceinline__ void ket_ctl_phi(KetEig& E, const double (&lam)[3], const double (&er)[3],
-                                            const double (&ei)[3], double dt) {
-  int e = 0;
-#pragma unroll
-  for (int k = 0; k < N; ++k)
-#pragma unroll
-    for (int l = k; l < N; ++l, ++e) {
-      if (k == l) {
-        E.P[e][0] = dt * ei[k];
-        E.P[e][1] = -dt * er[k];
-      } else {
-        double sn, cs;
-        sincos(0.5 * (lam[k] + lam[l]) * dt, &sn, &cs);
-        const double sc = dt * ket_sinc(0.5 * (lam[k] - lam[l]) * dt);
-        E.P[e][0] = -sc * sn;
-        E.P[e][1] = -sc * cs;
-      }
-    }
-}
-
 // Row i of dU'/dtheta (the lane's own; any other i gives zeros) in the real form of
 // ket_sched_row: out[2 j], out[2 j + 1] for column j.  F = 0: theta = a, cpl on the coupling
 // pattern; F = 1: theta = Delta.
@@ -218,84 +176,6 @@ __device__ __forceinline__ void ket_ctl_row(const KetEig& E, double cpl, int i, 
     }
     out[2 * j] = im ? ai : ar;
     out[2 * j + 1] = im ? ar : -ai;
-  }
-}
-
-// ket_blocks_build (ryd_engine.hip) statement for statement, so that B has its bits, and beside
-// it the eigen data of both blocks.  The 2 x 2 block's eigenvectors come from one Jacobi
-// rotation, exact for a 2 x 2 matrix.
-__device__ __forceinline__ void ket_blocks_build_ctl(KetBlocks& B, KetEig& E2, KetEig& E3, double a, double dl,
-                                                     double dt, double d1, double V) {
-  B.a = a;
-  B.dl = dl;
-  B.dt = dt;
-  {
-    const double c = 0.5 * (d1 - dl), h = 0.5 * (d1 + dl), w = 0.5 * a;
-    const double r = sqrt(fma(h, h, w * w));
-    double sr, cr, sc, cc;
-    sincos(r * dt, &sr, &cr);
-    sincos(c * dt, &sc, &cc);
-    const double snc = r > 0.0 ? sr / r : dt;
-    const double m[3][2] = {{cr, -snc * h}, {0.0, -snc * w}, {cr, snc * h}};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      B.u2[k][0] = fma(cc, m[k][0], sc * m[k][1]);
-      B.u2[k][1] = fma(cc, m[k][1], -sc * m[k][0]);
-    }
-    double A[3][3] = {{d1, w, 0.0}, {w, -dl, 0.0}, {0.0, 0.0, 0.0}};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) E2.Q[i][j] = i == j ? 1.0 : 0.0;
-    jacobi_rot(A, E2.Q, 0, 1);
-    const double lam[3] = {A[0][0], A[1][1], 0.0};
-    double er[3] = {1.0, 1.0, 1.0}, ei[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      double sn, cs;
-      sincos(lam[k] * dt, &sn, &cs);
-      er[k] = cs;
-      ei[k] = -sn;
-    }
-    ket_ctl_phi<2>(E2, lam, er, ei, dt);
-  }
-  {
-    const double g = a * 0.70710678118654752440;     // a / sqrt2
-    double A[3][3] = {{2.0 * d1, g, 0.0}, {g, d1 - dl, g}, {0.0, g, V - 2.0 * dl}};
-    double (&Q)[3][3] = E3.Q;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) Q[i][j] = i == j ? 1.0 : 0.0;
-#pragma unroll 1
-    for (int sweep = 0; sweep < 6; ++sweep) {
-      jacobi_rot(A, Q, 0, 1);
-      jacobi_rot(A, Q, 0, 2);
-      jacobi_rot(A, Q, 1, 2);
-    }
-    double er[3], ei[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      double sn, cs;
-      sincos(A[k][k] * dt, &sn, &cs);
-      er[k] = cs;
-      ei[k] = -sn;
-    }
-    const int I[6] = {0, 0, 0, 1, 1, 2}, J[6] = {0, 1, 2, 1, 2, 2};
-#pragma unroll
-    for (int e = 0; e < 6; ++e) {
-      double re = 0.0, im = 0.0;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const double w = Q[I[e]][k] * Q[J[e]][k];
-        re = fma(w, er[k], re);
-        im = fma(w, ei[k], im);
-      }
-      B.u3[e][0] = re;
-      B.u3[e][1] = im;
-    }
-    const double lam[3] = {A[0][0], A[1][1], A[2][2]};
-    ket_ctl_phi<3>(E3, lam, er, ei, dt);
   }
 }
 
@@ -353,19 +233,7 @@ __device__ __forceinline__ void ket_sched_body(const double* __restrict__ prm, i
     V = q.V;
     d1 = q.d1;
   }
-  // ---- the table's validity, one pass: lane r checks segments r, r + 16, ...
-  {
-    bool ok = true;
-    for (int s0 = 0; s0 < n_seg; s0 += 16) {
-      const double x = sched16_load(row, RYD_SC_X, n_seg, s0, r);
-      const double a = sched16_load(row, RYD_SC_AMP, n_seg, s0, r);
-      const double ph = sched16_load(row, RYD_SC_PHASE, n_seg, s0, r);
-      const double d = sched16_load(row, RYD_SC_DELTA, n_seg, s0, r);
-      ok = ok && x >= 0.0 && a >= 0.0 && isfinite(x) && isfinite(a) && isfinite(ph) && isfinite(d);
-    }
-    const uint64_t bad = __builtin_amdgcn_ballot_w64(!ok);
-    valid = valid && ((bad >> (16 * p)) & 0xFFFFull) == 0;
-  }
+  SCHED_TABLE_VALID(valid, row, n_seg, r, p)
   if (!valid) {                              // an invalid row builds identities of finite numbers
     Om = 1.0;
     V = d1 = 0.0;
@@ -374,14 +242,7 @@ __device__ __forceinline__ void ket_sched_body(const double* __restrict__ prm, i
   // the chunk at s0: lane r's segment s0 + r (clamped), its key, its phase; a capped segment
   // has the duration -1, an invalid row durations 0
   auto load_chunk = [&](int s0, double& Ka, double& Kd, double& Kt, double& Pc, double& Ps) {
-    const double x = sched16_load(row, RYD_SC_X, n_seg, s0, r);
-    const double a = sched16_load(row, RYD_SC_AMP, n_seg, s0, r);
-    const double ph = sched16_load(row, RYD_SC_PHASE, n_seg, s0, r);
-    const double d = sched16_load(row, RYD_SC_DELTA, n_seg, s0, r);
-    Ka = a * Om;
-    Kd = d * Om;
-    Kt = x / Om;
-    fast_sincos(ph, Ps, Pc);
+    SCHED_CHUNK_LOAD(row, n_seg, s0, r, Om)
     Seg g;
     g.om_re = Ka;
     g.om_im = 0.0;
@@ -391,9 +252,7 @@ __device__ __forceinline__ void ket_sched_body(const double* __restrict__ prm, i
     h_bounds(g, V, d1, emin, emax);
     if (!(0.5 * (emax - emin) * Kt <= X_CAP)) Kt = -1.0;
     if (!valid) {
-      Ka = Kd = Kt = 0.0;
-      Pc = 1.0;
-      Ps = 0.0;
+      SCHED_CHUNK_NEUTRAL()
     }
   };
 
@@ -465,11 +324,7 @@ __device__ __forceinline__ void ket_sched_body(const double* __restrict__ prm, i
       nuse += skip ? 0 : 1;
       cp = cs;
       sp = ss;
-      Ka = row_rol1(Ka);
-      Kd = row_rol1(Kd);
-      Kt = row_rol1(Kt);
-      Pc = row_rol1(Pc);
-      Ps = row_rol1(Ps);
+      SCHED_CHUNK_ROL1()
     }
   }
 
@@ -555,13 +410,7 @@ __device__ __forceinline__ void ket_sched_body(const double* __restrict__ prm, i
       double Ka, Kd, Kt, Pc, Ps;
       load_chunk(s0, Ka, Kd, Kt, Pc, Ps);
       const int cnt = min(16, n_seg - s0);
-      for (int k = cnt; k < 16; ++k) {       // a partial chunk: its last segment up to lane 15
-        Ka = row_ror1(Ka);
-        Kd = row_ror1(Kd);
-        Kt = row_ror1(Kt);
-        Pc = row_ror1(Pc);
-        Ps = row_ror1(Ps);
-      }
+      SCHED_CHUNK_TO_LANE15(cnt)
       double J0 = 0.0, J1 = 0.0, J2 = 0.0, J3 = 0.0;
       for (int j = cnt - 1; j >= 0; --j) {
         // segment s0 + j: lane 15 of the row after cnt - 1 - j rotations
@@ -592,11 +441,7 @@ __device__ __forceinline__ void ket_sched_body(const double* __restrict__ prm, i
         for (int c = 0; c < 4; ++c) g[c] = skip ? g[c] : gn[c];
         cp = cs;
         sp = ss;
-        Ka = row_ror1(Ka);
-        Kd = row_ror1(Kd);
-        Kt = row_ror1(Kt);
-        Pc = row_ror1(Pc);
-        Ps = row_ror1(Ps);
+        SCHED_CHUNK_ROR1()
       }
       if (active && r < cnt) {               // s0 + r <= n_seg - 1
         double* o = jac + (ip * ldj + (int64_t)s0 + r);
@@ -638,13 +483,7 @@ __device__ __forceinline__ void ket_sched_body(const double* __restrict__ prm, i
       double Ka, Kd, Kt, Pc, Ps;
       load_chunk(s0, Ka, Kd, Kt, Pc, Ps);
       const int cnt = min(16, n_seg - s0);
-      for (int k = cnt; k < 16; ++k) {
-        Ka = row_ror1(Ka);
-        Kd = row_ror1(Kd);
-        Kt = row_ror1(Kt);
-        Pc = row_ror1(Pc);
-        Ps = row_ror1(Ps);
-      }
+      SCHED_CHUNK_TO_LANE15(cnt)
       for (int j = cnt - 1; j >= 0; --j) {
         const double a = row_bcast<15>(Ka), dl = row_bcast<15>(Kd), dt = row_bcast<15>(Kt);
         const bool skip = !(dt > 0.0);
@@ -664,7 +503,7 @@ __device__ __forceinline__ void ket_sched_body(const double* __restrict__ prm, i
           Lt = need ? dt : Lt;
           KetBlocks K;
           KetEig E2, E3;
-          ket_blocks_build_ctl(K, E2, E3, La, Ld, Lt, d1, V);
+          ket_blocks_build<true>(K, La, Ld, Lt, d1, V, &E2, &E3);
           ket_sched_row(K, r, u);
           wave_sync();
 #pragma unroll
@@ -743,11 +582,7 @@ __device__ __forceinline__ void ket_sched_body(const double* __restrict__ prm, i
         for (int c = 0; c < 4; ++c) g[c] = skip ? g[c] : gn[c];
         cp = cs;
         sp = ss;
-        Ka = row_ror1(Ka);
-        Kd = row_ror1(Kd);
-        Kt = row_ror1(Kt);
-        Pc = row_ror1(Pc);
-        Ps = row_ror1(Ps);
+        SCHED_CHUNK_ROR1()
       }
       if (active && r < cnt) {               // s0 + r <= n_seg - 1: within the point's 16 n_seg
         double* o = jac + (ip * ldj + (int64_t)s0 + r);

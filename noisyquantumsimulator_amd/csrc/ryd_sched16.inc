@@ -8,15 +8,7 @@
 // with the segments read from the table: four points per wave, one 16-lane DPP row each,
 // build16 for a propagator, rotate_state / seg_apply per segment, sym16_epilogue at the end.
 //
-// Table.  Point-major, sched[i ld + f n_seg + s]; a shared table is the same address with
-// ld = 0.  It is read in chunks of 16 segments: lane r of a row loads segment s0 + r of each
-// of the four fields (one load instruction per field and chunk, 128 bytes per row), forms its
-// segment's key (a Omega, delta Omega, x / Omega) and the (cos, sin) of its phase -- sixteen
-// segments' worth per fast_sincos -- and the segment loop takes segment j's five values from
-// lane 0 of the row (row_newbcast) after j one-lane row rotations (DPP), never from memory.
-// Lanes past n_seg in the last chunk read segment n_seg - 1, a row past the batch reads point
-// n - 1: with ld >= 4 n_seg (checked on the host) the largest index formed is
-// (n - 1) ld + 4 n_seg - 1, the table's last element.  All of it is 64-bit arithmetic.
+// Table.  Read by the protocol of ryd_sched_table.inc (SCHED_TABLE_VALID, SCHED_CHUNK_*).
 //
 // Memo.  A propagator depends on (a Omega, delta Omega, x / Omega) and the point's scalars
 // only (the phase is carried by the frame), so a segment whose key equals -- ==, the three
@@ -27,33 +19,14 @@
 // executed, as in every kernel of this family).  Before the first build the row holds the
 // identity under the key (0, 0, 0), which no segment of positive duration equals.
 //
-// Validity.  One pass over the table before the first build: every entry finite, x >= 0,
-// a >= 0, and the point's scalars as bang-bang checks them (without its segment count; the
-// ignored column RYD_P_DELTA is not looked at).  An invalid row keeps its basis states -- it
-// takes part in no segment, and its builds are identities -- and is flagged BAD_INPUT.
+// Validity.  The pass of ryd_sched_table.inc.  An invalid row keeps its basis states -- it takes
+// part in no segment, and its builds are identities -- and is flagged BAD_INPUT.
 // A segment of duration zero (x_s / Omega == 0) is skipped and keeps the frame.
 //
 // Registers: the states, the frame, the chunk's values and the memo key are parked in LDS
 // across an in-loop build, as the bang-bang branch parks its states.
 
 constexpr int SC16_WAVES = 3;                // amdgpu_waves_per_eu: the bang-bang instantiation's budget
-
-// lane r takes the value of lane (r + 1) mod 16 of its row: row_ror:15, two 32-bit DPP moves
-__device__ __forceinline__ double row_rol1(double v) { return dpp32x2<0x12F>(v); }
-
-// the scalars a schedule point reads (load_point's columns OMEGA, V, DELTA1 and the rates)
-__device__ __forceinline__ bool sched16_point_valid(const PointP& q) {
-  bool ok = q.Om > 0.0 && isfinite(q.Om) && isfinite(q.V) && isfinite(q.d1);
-#pragma unroll
-  for (int c = 0; c < 4; ++c) ok = ok && q.gA[c] >= 0.0 && q.gB[c] >= 0.0 && isfinite(q.gA[c]) && isfinite(q.gB[c]);
-  return ok;
-}
-
-// field f of segment min(s0 + r, n_seg - 1) of the lane's row (row: the point's table row)
-__device__ __forceinline__ double sched16_load(const double* __restrict__ row, int f, int n_seg, int s0, int r) {
-  const int64_t s = (int64_t)s0 + r < (int64_t)n_seg ? (int64_t)s0 + r : (int64_t)n_seg - 1;
-  return row[(int64_t)f * (int64_t)n_seg + s];
-}
 
 template <bool STATE>
 __global__ __launch_bounds__(S16_BLOCK) __attribute__((amdgpu_waves_per_eu(SC16_WAVES, 8))) void
@@ -87,19 +60,7 @@ lindblad_sched16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, 
     const PointP q = load_point16<RYD_PROTO_LP_SQUARE>(prm, ldp, i0, po8);
     valid = sched16_point_valid(q);
   }
-  // ---- the table's validity, one pass: lane r checks segments r, r + 16, ...
-  {
-    bool ok = true;
-    for (int s0 = 0; s0 < n_seg; s0 += 16) {
-      const double x = sched16_load(row, RYD_SC_X, n_seg, s0, r);
-      const double a = sched16_load(row, RYD_SC_AMP, n_seg, s0, r);
-      const double ph = sched16_load(row, RYD_SC_PHASE, n_seg, s0, r);
-      const double d = sched16_load(row, RYD_SC_DELTA, n_seg, s0, r);
-      ok = ok && x >= 0.0 && a >= 0.0 && isfinite(x) && isfinite(a) && isfinite(ph) && isfinite(d);
-    }
-    const uint64_t bad = __builtin_amdgcn_ballot_w64(!ok);
-    valid = valid && ((bad >> (16 * p)) & 0xFFFFull) == 0;
-  }
+  SCHED_TABLE_VALID(valid, row, n_seg, r, p)
 
   // states: |11> triangle coordinate r; |01> atom-B coordinate r (r < 5); |00> scalar
   double t = (r == sym_index(1, 1)) ? 1.0 : 0.0;
@@ -123,18 +84,9 @@ lindblad_sched16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, 
       const double* pp = prm;
       asm volatile("" : "+s"(pp));           // re-read (an L1 hit), not kept live through the builds
       const double Om = pp[(int64_t)RYD_P_OMEGA * ldp + i0 + (int64_t)pc];
-      const double x = sched16_load(row, RYD_SC_X, n_seg, s0, r);
-      const double a = sched16_load(row, RYD_SC_AMP, n_seg, s0, r);
-      const double ph = sched16_load(row, RYD_SC_PHASE, n_seg, s0, r);
-      const double d = sched16_load(row, RYD_SC_DELTA, n_seg, s0, r);
-      Ka = a * Om;
-      Kd = d * Om;
-      Kt = x / Om;
-      fast_sincos(ph, Ps, Pc);
-      if (!valid) {                          // an invalid row takes part in nothing: no NaN reaches its states
-        Ka = Kd = Kt = 0.0;
-        Pc = 1.0;
-        Ps = 0.0;
+      SCHED_CHUNK_LOAD(row, n_seg, s0, r, Om)
+      if (!valid) {
+        SCHED_CHUNK_NEUTRAL()
       }
     }
     const int cnt = min(16, n_seg - s0);
@@ -204,11 +156,7 @@ lindblad_sched16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, 
         cp = cs;
         sp = ss;
       }
-      Ka = row_rol1(Ka);
-      Kd = row_rol1(Kd);
-      Kt = row_rol1(Kt);
-      Pc = row_rol1(Pc);
-      Ps = row_rol1(Ps);
+      SCHED_CHUNK_ROL1()
     }
   }
   // ---- back to the lab frame Q(cp, sp); the lane and point indices are recomputed here

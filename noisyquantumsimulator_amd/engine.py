@@ -289,6 +289,38 @@ def schedule_coherence_inputs(params: np.ndarray,
     return params, desc, tab, ld
 
 
+def param_block(params: np.ndarray) -> np.ndarray:
+    """``params`` as the contiguous float64 (NPARAM, n) block the library reads."""
+    params = np.ascontiguousarray(params, dtype=np.float64)
+    if params.shape[0] != N.NPARAM:
+        raise ValueError(f"params must have shape ({N.NPARAM}, n)")
+    return params
+
+
+def jacobian_shape(n: int, n_seg: int, controls: bool) -> Tuple[int, ...]:
+    """The library's Jacobian rows of a schedule-ket run: phases alone, or all four fields."""
+    return (n, N.SC_NFIELD, 4, n_seg) if controls else (n, N.SC_NFIELD, n_seg)
+
+
+def summary_result(evolution: str, n: int, state: Optional[np.ndarray], summ: np.ndarray, status: np.ndarray,
+                   dim: int, st: Optional[N.Stats] = None, jac: Optional[np.ndarray] = None,
+                   controls: bool = False) -> EngineResult:
+    """The EngineResult of a summary-carrying run: timings and iteration counts from the call's
+    stats, or (a device-resident batch, ``st`` None) no timings and the counts summed here;
+    ``jac`` the library's Jacobian rows of a schedule-ket run (``jacobian_shape``), or None."""
+    times = (st.kernel_ms, st.h2d_ms, st.d2h_ms, st.matvec_useful, st.matvec_exec) if st is not None else (
+        0.0, 0.0, 0.0, summ[N.S["NMV_USEFUL"]].sum(), summ[N.S["NMV_EXEC"]].sum())
+    if controls:
+        cj = complex_control_jacobian(jac)
+        return EngineResult(evolution, n, state, summ, status, *times, dim,
+                            np.ascontiguousarray(cj[:, N.SC["PHASE"]]), control_jacobian=cj)
+    return EngineResult(evolution, n, state, summ, status, *times, dim, complex_jacobian(jac))
+
+
+def _dptr(a: Optional[np.ndarray]):
+    return None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
 def sym16_balance_plan(n: int, cus: int = 256, gpc: int = 0) -> Dict[str, Any]:
     """The static plan of the sym16 LP-square kernel's CU-balanced launch form for ``n`` points
     on ``cus`` compute units (``gpc`` > 0 overrides the groups per workgroup): ``groups``,
@@ -357,6 +389,35 @@ class Engine:
         except Exception:
             pass
 
+    def _call(self, fn, desc, params: np.ndarray, outs, table=()) -> Tuple[np.ndarray, N.Stats]:
+        """One host-buffer entry point on ``params`` (NPARAM, n): ``table`` is the (pointer,
+        leading dimension) of a schedule table or nothing, ``outs`` the (array or None, leading
+        dimension) pairs in the entry point's order.  Returns (status (n,), the call's stats)."""
+        n = params.shape[1]
+        status = np.zeros(n, dtype=np.uint32)
+        st = N.Stats()
+        N.check(fn(self.handle, ctypes.byref(desc), _dptr(params), n, n, *table,
+                   *(x for arr, ld in outs for x in (_dptr(arr), ld)),
+                   status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(st)))
+        return status, st
+
+    def _summary_run(self, fn, desc, params: np.ndarray, evolution: str, dim: int, states: bool, table=(),
+                     jac: Optional[np.ndarray] = None, jac_arg: bool = False,
+                     controls: bool = False) -> EngineResult:
+        """A summary-carrying entry point and its EngineResult.  ``jac_arg``: the entry point takes
+        a Jacobian (``jac``, or NULL) after the summary."""
+        n = params.shape[1]
+        # every kernel writes every state row and summary column of every point, so the
+        # outputs need no zero fill (np.zeros of the 8 MB C2 state costs ~0.3 ms of page
+        # zeroing per call; tools/unpack_probe.py)
+        state = np.empty((N.STATE_WIDTH_DIM[dim][evolution], 4 * n), dtype=np.float64) if states else None
+        summ = np.empty((N.NSUMMARY, n), dtype=np.float64)
+        outs = [(state, 4 * n), (summ, n)]
+        if jac_arg:
+            outs.append((jac, (4 if controls else 1) * N.SC_NFIELD * desc.n_seg))
+        status, st = self._call(fn, desc, params, outs, table)
+        return summary_result(evolution, n, state, summ, status, dim, st, jac, controls)
+
     def run(self, params: np.ndarray, protocol: str, evolution: str, n_steps: Optional[int] = None,
             shape: str = "square", method: str = "chebyshev", rtol: float = 1e-10,
             atol: float = 1e-12, max_steps: int = 10 ** 7, dim: int = 3,
@@ -364,29 +425,12 @@ class Engine:
         """``states=False`` is a summary-only run: no state array is allocated, the library
         gets a NULL state pointer (no state rows cross the bus) and ``EngineResult.state`` is
         None; summary and status are those of the full run bit for bit."""
-        params = np.ascontiguousarray(params, dtype=np.float64)
-        if params.shape[0] != N.NPARAM:
-            raise ValueError(f"params must have shape ({N.NPARAM}, n)")
-        n = params.shape[1]
+        params = param_block(params)
         if n_steps is None:
             n_steps = default_n_steps(protocol, params)
         desc = make_desc(protocol, evolution, n_steps, shape, symmetric_atoms(params), method,
                          dim=dim, rtol=rtol, atol=atol, max_steps=max_steps)
-        w = N.STATE_WIDTH_DIM[dim][evolution]
-        # every kernel writes every state row and summary column of every point, so the
-        # outputs need no zero fill (np.zeros of the 8 MB C2 state costs ~0.3 ms of page
-        # zeroing per call; tools/unpack_probe.py)
-        state = np.empty((w, 4 * n), dtype=np.float64) if states else None
-        summ = np.empty((N.NSUMMARY, n), dtype=np.float64)
-        status = np.zeros(n, dtype=np.uint32)
-        st = N.Stats()
-        dptr = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-        N.check(self.lib.ryd_run_batch(
-            self.handle, ctypes.byref(desc), dptr(params), n, n, dptr(state) if states else None, 4 * n,
-            dptr(summ), n,
-            status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(st)))
-        return EngineResult(evolution, n, state, summ, status, st.kernel_ms, st.h2d_ms, st.d2h_ms,
-                            st.matvec_useful, st.matvec_exec, dim)
+        return self._summary_run(self.lib.ryd_run_batch, desc, params, evolution, dim, states)
 
     def run_schedule(self, params: np.ndarray, sched: np.ndarray, *, states: bool = True) -> EngineResult:
         """The caller's own pulse (ryd_run_schedule): ``sched`` is a table of piecewise-constant
@@ -394,22 +438,9 @@ class Engine:
         (``pulse_schedules``; fields ``_native.SC``).  Lindblad, dim 3, identical atoms: unequal
         atom-A / atom-B rate columns are refused.  The result is that of ``run(...,
         "lindblad")``; ``states=False`` is a summary-only run."""
-        params = np.ascontiguousarray(params, dtype=np.float64)
-        if params.shape[0] != N.NPARAM:
-            raise ValueError(f"params must have shape ({N.NPARAM}, n)")
-        n = params.shape[1]
+        params = param_block(params)
         desc, tab, ld = schedule_desc(params, sched)
-        state = np.empty((N.STATE_WIDTH["lindblad"], 4 * n), dtype=np.float64) if states else None
-        summ = np.empty((N.NSUMMARY, n), dtype=np.float64)
-        status = np.zeros(n, dtype=np.uint32)
-        st = N.Stats()
-        dptr = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-        N.check(self.lib.ryd_run_schedule(
-            self.handle, ctypes.byref(desc), dptr(params), n, n, dptr(tab), ld,
-            dptr(state) if states else None, 4 * n, dptr(summ), n,
-            status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(st)))
-        return EngineResult("lindblad", n, state, summ, status, st.kernel_ms, st.h2d_ms, st.d2h_ms,
-                            st.matvec_useful, st.matvec_exec, 3)
+        return self._summary_run(self.lib.ryd_run_schedule, desc, params, "lindblad", 3, states, (_dptr(tab), ld))
 
     def run_schedule_kets(self, params: np.ndarray, sched: np.ndarray, *, states: bool = True,
                           jacobian: Union[bool, str] = False) -> EngineResult:
@@ -424,34 +455,12 @@ class Engine:
         (first index ``_native.SC``, the table's units); ``phase_jacobian`` is then its
         ``SC["PHASE"]`` slice.  ``states=False`` is a summary-only run."""
         controls = jacobian_mode(jacobian)
-        params = np.ascontiguousarray(params, dtype=np.float64)
-        if params.shape[0] != N.NPARAM:
-            raise ValueError(f"params must have shape ({N.NPARAM}, n)")
-        n = params.shape[1]
+        params = param_block(params)
         desc, tab, ld = schedule_desc(params, sched)
-        state = np.empty((N.STATE_WIDTH["ket"], 4 * n), dtype=np.float64) if states else None
-        summ = np.empty((N.NSUMMARY, n), dtype=np.float64)
-        status = np.zeros(n, dtype=np.uint32)
-        st = N.Stats()
-        dptr = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-        if controls:
-            jac = np.empty((n, N.SC_NFIELD, 4, desc.n_seg), dtype=np.float64)
-            N.check(self.lib.ryd_run_schedule_kets_ctl(
-                self.handle, ctypes.byref(desc), dptr(params), n, n, dptr(tab), ld,
-                dptr(state) if states else None, 4 * n, dptr(summ), n, dptr(jac), 4 * N.SC_NFIELD * desc.n_seg,
-                status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(st)))
-            cj = complex_control_jacobian(jac)
-            return EngineResult("ket", n, state, summ, status, st.kernel_ms, st.h2d_ms, st.d2h_ms,
-                                st.matvec_useful, st.matvec_exec, 3,
-                                np.ascontiguousarray(cj[:, N.SC["PHASE"]]), control_jacobian=cj)
-        jac = np.empty((n, N.SC_NFIELD, desc.n_seg), dtype=np.float64) if jacobian else None
-        N.check(self.lib.ryd_run_schedule_kets(
-            self.handle, ctypes.byref(desc), dptr(params), n, n, dptr(tab), ld,
-            dptr(state) if states else None, 4 * n, dptr(summ), n,
-            dptr(jac) if jacobian else None, N.SC_NFIELD * desc.n_seg,
-            status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(st)))
-        return EngineResult("ket", n, state, summ, status, st.kernel_ms, st.h2d_ms, st.d2h_ms,
-                            st.matvec_useful, st.matvec_exec, 3, complex_jacobian(jac))
+        n = params.shape[1]
+        jac = np.empty(jacobian_shape(n, desc.n_seg, controls), dtype=np.float64) if jacobian else None
+        fn = self.lib.ryd_run_schedule_kets_ctl if controls else self.lib.ryd_run_schedule_kets
+        return self._summary_run(fn, desc, params, "ket", 3, states, (_dptr(tab), ld), jac, True, controls)
 
     def last_timeline(self) -> Dict[str, Any]:
         """ryd_last_timeline: host staging times and the per-slot HIP-event timeline of the
@@ -471,21 +480,14 @@ class Engine:
         """The 6 upper off-diagonal qubit matrix units through the gate
         (ryd_run_coherences): returns (coh (NCOH, n) float64, status (n,) uint32).  The rows
         mean the same for ``dim`` 3 and 4 (the qubit block has the same support)."""
-        params = np.ascontiguousarray(params, dtype=np.float64)
-        if params.shape[0] != N.NPARAM:
-            raise ValueError(f"params must have shape ({N.NPARAM}, n)")
+        params = param_block(params)
         check_coherence_dim(params, dim)
         n = params.shape[1]
         if n_steps is None:
             n_steps = default_n_steps(protocol, params)
         desc = make_desc(protocol, "lindblad", n_steps, shape, symmetric_atoms(params), "cheb_vector", dim=dim)
         coh = np.zeros((N.NCOH, n), dtype=np.float64)
-        status = np.zeros(n, dtype=np.uint32)
-        st = N.Stats()
-        dptr = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-        N.check(self.lib.ryd_run_coherences(
-            self.handle, ctypes.byref(desc), dptr(params), n, n, dptr(coh), n,
-            status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(st)))
+        status, _ = self._call(self.lib.ryd_run_coherences, desc, params, [(coh, n)])
         return coh, status
 
     def run_schedule_coherences(self, params: np.ndarray, sched: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
@@ -496,12 +498,7 @@ class Engine:
         params, desc, tab, ld = schedule_coherence_inputs(params, sched)
         n = params.shape[1]
         coh = np.zeros((N.NCOH, n), dtype=np.float64)
-        status = np.zeros(n, dtype=np.uint32)
-        st = N.Stats()
-        dptr = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-        N.check(self.lib.ryd_run_schedule_coherences(
-            self.handle, ctypes.byref(desc), dptr(params), n, n, dptr(tab), ld, dptr(coh), n,
-            status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(st)))
+        status, _ = self._call(self.lib.ryd_run_schedule_coherences, desc, params, [(coh, n)], (_dptr(tab), ld))
         return coh, status
 
     def derive(self, inp, diag: bool = False) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
@@ -551,15 +548,83 @@ class Engine:
         return out, status
 
 
-class DeviceBatch:
+class _DeviceBuffers:
+    """What every device-resident batch shares: buffers on one device slot (allocated with a
+    16-byte floor, freed together), uploads and downloads through the slot's stream, the two
+    HIP-event marks, and the timing of a ``*_device`` call.  A subclass keeps its constructor
+    arguments, its ``launch`` and what ``fetch`` assembles."""
+
+    def __init__(self, engine: Engine, slot: int):
+        self.eng, self.slot = engine, slot
+        self._bufs = []
+
+    def _alloc(self, nbytes: int) -> ctypes.c_void_p:
+        p = ctypes.c_void_p()
+        N.check(self.eng.lib.ryd_malloc(self.eng.handle, self.slot, max(nbytes, 16), ctypes.byref(p)))
+        self._bufs.append(p)
+        return p
+
+    def _upload(self, array: np.ndarray, d_ptr: Optional[ctypes.c_void_p] = None) -> ctypes.c_void_p:
+        """H2D of a contiguous array, into a new buffer of its size unless ``d_ptr`` is given."""
+        if d_ptr is None:
+            d_ptr = self._alloc(array.nbytes)
+        N.check(self.eng.lib.ryd_memcpy_h2d(self.eng.handle, self.slot, d_ptr, array.ctypes.data, array.nbytes))
+        return d_ptr
+
+    def _download(self, array: np.ndarray, d_ptr: ctypes.c_void_p) -> np.ndarray:
+        N.check(self.eng.lib.ryd_memcpy_d2h(self.eng.handle, self.slot, array.ctypes.data, d_ptr, array.nbytes))
+        return array
+
+    def _timed(self, call, timed: bool) -> float:
+        """``call(elapsed_ms)`` with a float pointer when ``timed`` (the library then waits and
+        reports the device time between HIP events on the launch stream), else NULL."""
+        ms = ctypes.c_float(0.0)
+        N.check(call(ctypes.byref(ms) if timed else None))
+        return float(ms.value)
+
+    def _alloc_summary_run(self, n: int, states: bool) -> None:
+        """The outputs of a summary-carrying run; ``states`` False: summary-only, no d_state
+        (NULL is passed)."""
+        self.states = states
+        self.d_state = self._alloc(8 * self.width * 4 * n) if states else None
+        self.d_summary = self._alloc(8 * N.NSUMMARY * n)
+        self.d_status = self._alloc(4 * n)
+
+    def _fetch_summary_run(self, evolution: str, dim: int, status_or=0, jac: Optional[np.ndarray] = None,
+                           controls: bool = False) -> EngineResult:
+        state = self._download(np.zeros((self.width, 4 * self.n)), self.d_state) if self.states else None
+        summ = self._download(np.zeros((N.NSUMMARY, self.n)), self.d_summary)
+        status = self._download(np.zeros(self.n, dtype=np.uint32), self.d_status)
+        return summary_result(evolution, self.n, state, summ, status | status_or, dim, None, jac, controls)
+
+    def _fetch_coherences(self) -> Tuple[np.ndarray, np.ndarray]:
+        return (self._download(np.zeros((N.NCOH, self.n)), self.d_coh),
+                self._download(np.zeros(self.n, dtype=np.uint32), self.d_status))
+
+    def mark(self, which: int):
+        """Record HIP event `which` (0 = region start, 1 = region end) on the launch stream."""
+        N.check(self.eng.lib.ryd_mark(self.eng.handle, self.slot, which))
+
+    def mark_elapsed(self) -> float:
+        """Device ms between marks 0 and 1 (waits for mark 1)."""
+        return self._timed(lambda ms: self.eng.lib.ryd_mark_elapsed(self.eng.handle, self.slot, ms), True)
+
+    def synchronize(self):
+        N.check(self.eng.lib.ryd_synchronize(self.eng.handle))
+
+    def free(self):
+        for p in self._bufs:
+            self.eng.lib.ryd_free(self.eng.handle, self.slot, p)
+        self._bufs = []
+
+
+class DeviceBatch(_DeviceBuffers):
     """Inputs resident in HBM on one device slot, for timed re-runs (bench.py)."""
 
     def __init__(self, engine: Engine, params: np.ndarray, protocol: str, evolution: str,
                  n_steps: Optional[int] = None, shape: str = "square", slot: int = 0,
                  method: str = "chebyshev", dim: int = 3, states: bool = True):
-        self.eng, self.slot = engine, slot
-        self.states = states                 # False: summary-only, no d_state (NULL is passed)
-        lib = engine.lib
+        super().__init__(engine, slot)
         params = np.ascontiguousarray(params, dtype=np.float64)
         self.n = n = params.shape[1]
         if n_steps is None:
@@ -568,122 +633,48 @@ class DeviceBatch:
         self.dim = dim
         self.width = N.STATE_WIDTH_DIM[dim][evolution]
         self.evolution = evolution
-        self._bufs = []
-
-        def alloc(nbytes):
-            p = ctypes.c_void_p()
-            N.check(lib.ryd_malloc(engine.handle, slot, nbytes, ctypes.byref(p)))
-            self._bufs.append(p)
-            return p
-        self.d_params = alloc(params.nbytes)
-        self.d_state = alloc(8 * self.width * 4 * n) if states else None
-        self.d_summary = alloc(8 * N.NSUMMARY * n)
-        self.d_status = alloc(4 * n)
-        N.check(lib.ryd_memcpy_h2d(engine.handle, slot, self.d_params, params.ctypes.data, params.nbytes))
+        self.d_params = self._upload(params)
+        self._alloc_summary_run(n, states)
 
     def launch(self, timed: bool = False) -> float:
         """Enqueue one propagation of the whole batch; with ``timed`` wait and return
         the kernel's device time (HIP events on the launch stream)."""
-        ms = ctypes.c_float(0.0)
-        N.check(self.eng.lib.ryd_run_batch_device(
+        return self._timed(lambda ms: self.eng.lib.ryd_run_batch_device(
             self.eng.handle, self.slot, ctypes.byref(self.desc), self.d_params, self.n, self.n,
-            self.d_state, 4 * self.n, self.d_summary, self.n, self.d_status, None,
-            ctypes.byref(ms) if timed else None))
-        return float(ms.value)
-
-    def mark(self, which: int):
-        """Record HIP event `which` (0 = region start, 1 = region end) on the launch stream."""
-        N.check(self.eng.lib.ryd_mark(self.eng.handle, self.slot, which))
-
-    def mark_elapsed(self) -> float:
-        """Device ms between marks 0 and 1 (waits for mark 1)."""
-        ms = ctypes.c_float(0.0)
-        N.check(self.eng.lib.ryd_mark_elapsed(self.eng.handle, self.slot, ctypes.byref(ms)))
-        return float(ms.value)
-
-    def synchronize(self):
-        N.check(self.eng.lib.ryd_synchronize(self.eng.handle))
+            self.d_state, 4 * self.n, self.d_summary, self.n, self.d_status, None, ms), timed)
 
     def fetch(self) -> EngineResult:
-        lib, h, s = self.eng.lib, self.eng.handle, self.slot
-        state = np.zeros((self.width, 4 * self.n)) if self.states else None
-        summ = np.zeros((N.NSUMMARY, self.n))
-        status = np.zeros(self.n, dtype=np.uint32)
-        if self.states:
-            N.check(lib.ryd_memcpy_d2h(h, s, state.ctypes.data, self.d_state, state.nbytes))
-        N.check(lib.ryd_memcpy_d2h(h, s, summ.ctypes.data, self.d_summary, summ.nbytes))
-        N.check(lib.ryd_memcpy_d2h(h, s, status.ctypes.data, self.d_status, status.nbytes))
-        return EngineResult(self.evolution, self.n, state, summ, status, 0.0, 0.0, 0.0,
-                            summ[N.S["NMV_USEFUL"]].sum(), summ[N.S["NMV_EXEC"]].sum(), self.dim)
-
-    def free(self):
-        for p in self._bufs:
-            self.eng.lib.ryd_free(self.eng.handle, self.slot, p)
-        self._bufs = []
+        return self._fetch_summary_run(self.evolution, self.dim)
 
 
-class ScheduleDeviceBatch:
+class ScheduleDeviceBatch(_DeviceBuffers):
     """A schedule run (ryd_run_schedule_device) with parameters and table resident in HBM on
     one device slot, for timed re-runs; ``sched`` as ``Engine.run_schedule`` takes it."""
 
     def __init__(self, engine: Engine, params: np.ndarray, sched: np.ndarray, slot: int = 0,
                  states: bool = True):
-        self.eng, self.slot = engine, slot
-        self.states = states                 # False: summary-only, no d_state (NULL is passed)
-        lib = engine.lib
-        params = np.ascontiguousarray(params, dtype=np.float64)
-        if params.shape[0] != N.NPARAM:
-            raise ValueError(f"params must have shape ({N.NPARAM}, n)")
+        super().__init__(engine, slot)
+        params = param_block(params)
         self.n = n = params.shape[1]
         self.desc, tab, self.ld_sched = schedule_desc(params, sched)
         self.width = N.STATE_WIDTH["lindblad"]
-        self._bufs = []
-
-        def alloc(nbytes):
-            p = ctypes.c_void_p()
-            N.check(lib.ryd_malloc(engine.handle, slot, max(nbytes, 16), ctypes.byref(p)))
-            self._bufs.append(p)
-            return p
-        self.d_params = alloc(params.nbytes)
-        self.d_sched = alloc(tab.nbytes)
-        self.d_state = alloc(8 * self.width * 4 * n) if states else None
-        self.d_summary = alloc(8 * N.NSUMMARY * n)
-        self.d_status = alloc(4 * n)
-        N.check(lib.ryd_memcpy_h2d(engine.handle, slot, self.d_params, params.ctypes.data, params.nbytes))
-        N.check(lib.ryd_memcpy_h2d(engine.handle, slot, self.d_sched, tab.ctypes.data, tab.nbytes))
+        self.d_params = self._upload(params)
+        self.d_sched = self._upload(tab)
+        self._alloc_summary_run(n, states)
 
     def launch(self, timed: bool = False) -> float:
         """Enqueue one propagation of the whole batch; with ``timed`` wait and return the
         kernel's device time (HIP events on the launch stream)."""
-        ms = ctypes.c_float(0.0)
-        N.check(self.eng.lib.ryd_run_schedule_device(
+        return self._timed(lambda ms: self.eng.lib.ryd_run_schedule_device(
             self.eng.handle, self.slot, ctypes.byref(self.desc), self.d_params, self.n, self.n,
             self.d_sched, self.ld_sched, self.d_state, 4 * self.n, self.d_summary, self.n, self.d_status, None,
-            ctypes.byref(ms) if timed else None))
-        return float(ms.value)
-
-    def synchronize(self):
-        N.check(self.eng.lib.ryd_synchronize(self.eng.handle))
+            ms), timed)
 
     def fetch(self) -> EngineResult:
-        lib, h, s = self.eng.lib, self.eng.handle, self.slot
-        state = np.zeros((self.width, 4 * self.n)) if self.states else None
-        summ = np.zeros((N.NSUMMARY, self.n))
-        status = np.zeros(self.n, dtype=np.uint32)
-        if self.states:
-            N.check(lib.ryd_memcpy_d2h(h, s, state.ctypes.data, self.d_state, state.nbytes))
-        N.check(lib.ryd_memcpy_d2h(h, s, summ.ctypes.data, self.d_summary, summ.nbytes))
-        N.check(lib.ryd_memcpy_d2h(h, s, status.ctypes.data, self.d_status, status.nbytes))
-        return EngineResult("lindblad", self.n, state, summ, status, 0.0, 0.0, 0.0,
-                            summ[N.S["NMV_USEFUL"]].sum(), summ[N.S["NMV_EXEC"]].sum(), 3)
-
-    def free(self):
-        for p in self._bufs:
-            self.eng.lib.ryd_free(self.eng.handle, self.slot, p)
-        self._bufs = []
+        return self._fetch_summary_run("lindblad", 3)
 
 
-class ScheduleKetDeviceBatch:
+class ScheduleKetDeviceBatch(_DeviceBuffers):
     """A noise-free schedule run as kets (ryd_run_schedule_kets_device) with parameters and table
     resident in HBM on one device slot, for timed re-runs, in the manner of
     ``ScheduleDeviceBatch``; ``sched``, ``states`` and ``jacobian`` as
@@ -691,79 +682,37 @@ class ScheduleKetDeviceBatch:
 
     def __init__(self, engine: Engine, params: np.ndarray, sched: np.ndarray, slot: int = 0,
                  states: bool = True, jacobian: Union[bool, str] = False):
-        self.eng, self.slot = engine, slot
+        super().__init__(engine, slot)
         self.controls = jacobian_mode(jacobian)         # "controls": ryd_run_schedule_kets_ctl_device
-        self.states, self.jacobian = states, jacobian   # False: no buffer, NULL is passed
-        lib = engine.lib
-        params = np.ascontiguousarray(params, dtype=np.float64)
-        if params.shape[0] != N.NPARAM:
-            raise ValueError(f"params must have shape ({N.NPARAM}, n)")
+        self.jacobian = jacobian                        # False: no buffer, NULL is passed
+        params = param_block(params)
         self.n = n = params.shape[1]
         self.desc, tab, self.ld_sched = schedule_desc(params, sched)
         self.width = N.STATE_WIDTH["ket"]
         self.ld_jac = (4 if self.controls else 1) * N.SC_NFIELD * self.desc.n_seg
-        self._bufs = []
-
-        def alloc(nbytes):
-            p = ctypes.c_void_p()
-            N.check(lib.ryd_malloc(engine.handle, slot, max(nbytes, 16), ctypes.byref(p)))
-            self._bufs.append(p)
-            return p
-        self.d_params = alloc(params.nbytes)
-        self.d_sched = alloc(tab.nbytes)
-        self.d_state = alloc(8 * self.width * 4 * n) if states else None
-        self.d_summary = alloc(8 * N.NSUMMARY * n)
-        self.d_jac = alloc(8 * self.ld_jac * n) if jacobian else None
-        self.d_status = alloc(4 * n)
-        N.check(lib.ryd_memcpy_h2d(engine.handle, slot, self.d_params, params.ctypes.data, params.nbytes))
-        N.check(lib.ryd_memcpy_h2d(engine.handle, slot, self.d_sched, tab.ctypes.data, tab.nbytes))
+        self.d_params = self._upload(params)
+        self.d_sched = self._upload(tab)
+        self._alloc_summary_run(n, states)
+        self.d_jac = self._alloc(8 * self.ld_jac * n) if jacobian else None
 
     def launch(self, timed: bool = False) -> float:
         """Enqueue one propagation of the whole batch; with ``timed`` wait and return the
         kernel's device time (HIP events on the launch stream)."""
-        ms = ctypes.c_float(0.0)
         lib = self.eng.lib
         fn = lib.ryd_run_schedule_kets_ctl_device if self.controls else lib.ryd_run_schedule_kets_device
-        N.check(fn(
+        return self._timed(lambda ms: fn(
             self.eng.handle, self.slot, ctypes.byref(self.desc), self.d_params, self.n, self.n,
             self.d_sched, self.ld_sched, self.d_state, 4 * self.n, self.d_summary, self.n,
-            self.d_jac, self.ld_jac, self.d_status, None, ctypes.byref(ms) if timed else None))
-        return float(ms.value)
-
-    def synchronize(self):
-        N.check(self.eng.lib.ryd_synchronize(self.eng.handle))
+            self.d_jac, self.ld_jac, self.d_status, None, ms), timed)
 
     def fetch(self) -> EngineResult:
-        lib, h, s = self.eng.lib, self.eng.handle, self.slot
-        state = np.zeros((self.width, 4 * self.n)) if self.states else None
-        summ = np.zeros((N.NSUMMARY, self.n))
         jac = None
-        if self.controls:
-            jac = np.zeros((self.n, N.SC_NFIELD, 4, self.desc.n_seg))
-        elif self.jacobian:
-            jac = np.zeros((self.n, N.SC_NFIELD, self.desc.n_seg))
-        status = np.zeros(self.n, dtype=np.uint32)
-        if self.states:
-            N.check(lib.ryd_memcpy_d2h(h, s, state.ctypes.data, self.d_state, state.nbytes))
         if self.jacobian:
-            N.check(lib.ryd_memcpy_d2h(h, s, jac.ctypes.data, self.d_jac, jac.nbytes))
-        N.check(lib.ryd_memcpy_d2h(h, s, summ.ctypes.data, self.d_summary, summ.nbytes))
-        N.check(lib.ryd_memcpy_d2h(h, s, status.ctypes.data, self.d_status, status.nbytes))
-        if self.controls:
-            cj = complex_control_jacobian(jac)
-            return EngineResult("ket", self.n, state, summ, status, 0.0, 0.0, 0.0,
-                                summ[N.S["NMV_USEFUL"]].sum(), summ[N.S["NMV_EXEC"]].sum(), 3,
-                                np.ascontiguousarray(cj[:, N.SC["PHASE"]]), control_jacobian=cj)
-        return EngineResult("ket", self.n, state, summ, status, 0.0, 0.0, 0.0,
-                            summ[N.S["NMV_USEFUL"]].sum(), summ[N.S["NMV_EXEC"]].sum(), 3, complex_jacobian(jac))
-
-    def free(self):
-        for p in self._bufs:
-            self.eng.lib.ryd_free(self.eng.handle, self.slot, p)
-        self._bufs = []
+            jac = self._download(np.zeros(jacobian_shape(self.n, self.desc.n_seg, self.controls)), self.d_jac)
+        return self._fetch_summary_run("ket", 3, jac=jac, controls=self.controls)
 
 
-class DeviceSweep:
+class DeviceSweep(_DeviceBuffers):
     """A sweep whose parameters never exist on the host: its varying input fields are
     resident on one device slot (``upload``), ``ryd_derive_device`` writes the parameter
     block in HBM and the propagation kernel reads it there (C4: 1M species x T x
@@ -772,9 +721,8 @@ class DeviceSweep:
 
     def __init__(self, engine: Engine, inp, evolution: str = "lindblad", slot: int = 0,
                  n_steps: Optional[int] = None, method: str = "chebyshev", states: bool = True):
-        self.eng, self.slot, self.inp = engine, slot, inp
-        self.states = states                 # False: summary-only, no d_state (NULL is passed)
-        lib = engine.lib
+        super().__init__(engine, slot)
+        self.inp = inp
         self.n = n = inp.n
         self.dim = inp.dim
         self.width = N.STATE_WIDTH_DIM[inp.dim][evolution]
@@ -785,93 +733,48 @@ class DeviceSweep:
                 n_steps = int(inp.desc.bb_nseg)
         # every shared rate is equal on both atoms (the derivation writes atom B = atom A)
         self.desc = make_desc(inp.protocol, evolution, n_steps, inp.shape, True, method, dim=inp.dim)
-        self._bufs = []
-
-        def alloc(nbytes):
-            p = ctypes.c_void_p()
-            N.check(lib.ryd_malloc(engine.handle, slot, max(nbytes, 16), ctypes.byref(p)))
-            self._bufs.append(p)
-            return p
         self.k = inp.cols.shape[0]
-        self.d_in = alloc(8 * self.k * n)
-        self.d_params = alloc(8 * N.NPARAM * n)
-        self.d_warn = alloc(4 * n)
-        self.d_state = alloc(8 * self.width * 4 * n) if states else None
-        self.d_summary = alloc(8 * N.NSUMMARY * n)
-        self.d_status = alloc(4 * n)
+        self.d_in = self._alloc(8 * self.k * n)
+        self.d_params = self._alloc(8 * N.NPARAM * n)
+        self.d_warn = self._alloc(4 * n)
+        self._alloc_summary_run(n, states)
         self.upload()
 
     def upload(self):
         """H2D of the varying input fields (the only per-point host data)."""
-        cols = np.ascontiguousarray(self.inp.cols, dtype=np.float64)
         if self.k:
-            N.check(self.eng.lib.ryd_memcpy_h2d(self.eng.handle, self.slot, self.d_in, cols.ctypes.data, cols.nbytes))
+            self._upload(np.ascontiguousarray(self.inp.cols, dtype=np.float64), self.d_in)
 
     def derive(self, timed: bool = False) -> float:
-        ms = ctypes.c_float(0.0)
-        N.check(self.eng.lib.ryd_derive_device(
+        return self._timed(lambda ms: self.eng.lib.ryd_derive_device(
             self.eng.handle, self.slot, ctypes.byref(self.inp.desc), self.d_in if self.k else None, self.n,
-            self.n, self.d_params, self.n, self.d_warn, None, self.n, None, ctypes.byref(ms) if timed else None))
-        return float(ms.value)
+            self.n, self.d_params, self.n, self.d_warn, None, self.n, None, ms), timed)
 
     def propagate(self, timed: bool = False) -> float:
-        ms = ctypes.c_float(0.0)
-        N.check(self.eng.lib.ryd_run_batch_device(
+        return self._timed(lambda ms: self.eng.lib.ryd_run_batch_device(
             self.eng.handle, self.slot, ctypes.byref(self.desc), self.d_params, self.n, self.n,
-            self.d_state, 4 * self.n, self.d_summary, self.n, self.d_status, None,
-            ctypes.byref(ms) if timed else None))
-        return float(ms.value)
+            self.d_state, 4 * self.n, self.d_summary, self.n, self.d_status, None, ms), timed)
 
     def launch(self):
         self.derive()
         self.propagate()
 
-    def mark(self, which: int):
-        N.check(self.eng.lib.ryd_mark(self.eng.handle, self.slot, which))
-
-    def mark_elapsed(self) -> float:
-        ms = ctypes.c_float(0.0)
-        N.check(self.eng.lib.ryd_mark_elapsed(self.eng.handle, self.slot, ctypes.byref(ms)))
-        return float(ms.value)
-
-    def synchronize(self):
-        N.check(self.eng.lib.ryd_synchronize(self.eng.handle))
-
     def fetch_params(self) -> Tuple[np.ndarray, np.ndarray]:
-        lib, h, s = self.eng.lib, self.eng.handle, self.slot
-        p = np.zeros((N.NPARAM, self.n))
-        w = np.zeros(self.n, dtype=np.uint32)
-        N.check(lib.ryd_memcpy_d2h(h, s, p.ctypes.data, self.d_params, p.nbytes))
-        N.check(lib.ryd_memcpy_d2h(h, s, w.ctypes.data, self.d_warn, w.nbytes))
-        return p, w
+        return (self._download(np.zeros((N.NPARAM, self.n)), self.d_params),
+                self._download(np.zeros(self.n, dtype=np.uint32), self.d_warn))
 
     def fetch(self) -> EngineResult:
-        lib, h, s = self.eng.lib, self.eng.handle, self.slot
-        state = np.zeros((self.width, 4 * self.n)) if self.states else None
-        summ = np.zeros((N.NSUMMARY, self.n))
-        status = np.zeros(self.n, dtype=np.uint32)
-        if self.states:
-            N.check(lib.ryd_memcpy_d2h(h, s, state.ctypes.data, self.d_state, state.nbytes))
-        N.check(lib.ryd_memcpy_d2h(h, s, summ.ctypes.data, self.d_summary, summ.nbytes))
-        N.check(lib.ryd_memcpy_d2h(h, s, status.ctypes.data, self.d_status, status.nbytes))
         _, warn = self.fetch_params()
-        return EngineResult(self.evolution, self.n, state, summ, status | warn, 0.0, 0.0, 0.0,
-                            summ[N.S["NMV_USEFUL"]].sum(), summ[N.S["NMV_EXEC"]].sum(), self.dim)
-
-    def free(self):
-        for p in self._bufs:
-            self.eng.lib.ryd_free(self.eng.handle, self.slot, p)
-        self._bufs = []
+        return self._fetch_summary_run(self.evolution, self.dim, status_or=warn)
 
 
-class CoherenceDeviceBatch:
+class CoherenceDeviceBatch(_DeviceBuffers):
     """Process-map coherence sectors (ryd_run_coherences_device: one launch of the dim-3 or
     dim-4 coherence kernel) with inputs resident in HBM, for timed re-runs."""
 
     def __init__(self, engine: Engine, params: np.ndarray, protocol: str, n_steps: Optional[int] = None,
                  shape: str = "square", slot: int = 0, dim: int = 3):
-        self.eng, self.slot = engine, slot
-        lib = engine.lib
+        super().__init__(engine, slot)
         params = np.ascontiguousarray(params, dtype=np.float64)
         check_coherence_dim(params, dim)
         self.dim = dim
@@ -880,103 +783,38 @@ class CoherenceDeviceBatch:
             n_steps = default_n_steps(protocol, params)
         self.desc = make_desc(protocol, "lindblad", n_steps, shape, symmetric_atoms(params), "cheb_vector",
                               dim=dim)
-        self._bufs = []
-
-        def alloc(nbytes):
-            p = ctypes.c_void_p()
-            N.check(lib.ryd_malloc(engine.handle, slot, nbytes, ctypes.byref(p)))
-            self._bufs.append(p)
-            return p
-        self.d_params = alloc(params.nbytes)
-        self.d_coh = alloc(8 * N.NCOH * n)
-        self.d_status = alloc(4 * n)
-        N.check(lib.ryd_memcpy_h2d(engine.handle, slot, self.d_params, params.ctypes.data, params.nbytes))
+        self.d_params = self._upload(params)
+        self.d_coh = self._alloc(8 * N.NCOH * n)
+        self.d_status = self._alloc(4 * n)
 
     def launch(self, timed: bool = False) -> float:
-        ms = ctypes.c_float(0.0)
-        N.check(self.eng.lib.ryd_run_coherences_device(
+        return self._timed(lambda ms: self.eng.lib.ryd_run_coherences_device(
             self.eng.handle, self.slot, ctypes.byref(self.desc), self.d_params, self.n, self.n,
-            self.d_coh, self.n, self.d_status, None, ctypes.byref(ms) if timed else None))
-        return float(ms.value)
-
-    def mark(self, which: int):
-        N.check(self.eng.lib.ryd_mark(self.eng.handle, self.slot, which))
-
-    def mark_elapsed(self) -> float:
-        ms = ctypes.c_float(0.0)
-        N.check(self.eng.lib.ryd_mark_elapsed(self.eng.handle, self.slot, ctypes.byref(ms)))
-        return float(ms.value)
-
-    def synchronize(self):
-        N.check(self.eng.lib.ryd_synchronize(self.eng.handle))
+            self.d_coh, self.n, self.d_status, None, ms), timed)
 
     def fetch(self) -> Tuple[np.ndarray, np.ndarray]:
-        lib, h, s = self.eng.lib, self.eng.handle, self.slot
-        coh = np.zeros((N.NCOH, self.n))
-        status = np.zeros(self.n, dtype=np.uint32)
-        N.check(lib.ryd_memcpy_d2h(h, s, coh.ctypes.data, self.d_coh, coh.nbytes))
-        N.check(lib.ryd_memcpy_d2h(h, s, status.ctypes.data, self.d_status, status.nbytes))
-        return coh, status
-
-    def free(self):
-        for p in self._bufs:
-            self.eng.lib.ryd_free(self.eng.handle, self.slot, p)
-        self._bufs = []
+        return self._fetch_coherences()
 
 
-class ScheduleCoherenceDeviceBatch:
+class ScheduleCoherenceDeviceBatch(_DeviceBuffers):
     """The coherence sectors of a schedule (ryd_run_schedule_coherences_device) with parameters
     and table resident in HBM on one device slot, for timed re-runs: the interface of
     ``CoherenceDeviceBatch``, ``sched`` as ``Engine.run_schedule_coherences`` takes it."""
 
     def __init__(self, engine: Engine, params: np.ndarray, sched: np.ndarray, slot: int = 0):
-        self.eng, self.slot = engine, slot
-        lib = engine.lib
+        super().__init__(engine, slot)
         params, self.desc, tab, self.ld_sched = schedule_coherence_inputs(params, sched)
         self.dim = 3
         self.n = n = params.shape[1]
-        self._bufs = []
-
-        def alloc(nbytes):
-            p = ctypes.c_void_p()
-            N.check(lib.ryd_malloc(engine.handle, slot, max(nbytes, 16), ctypes.byref(p)))
-            self._bufs.append(p)
-            return p
-        self.d_params = alloc(params.nbytes)
-        self.d_sched = alloc(tab.nbytes)
-        self.d_coh = alloc(8 * N.NCOH * n)
-        self.d_status = alloc(4 * n)
-        N.check(lib.ryd_memcpy_h2d(engine.handle, slot, self.d_params, params.ctypes.data, params.nbytes))
-        N.check(lib.ryd_memcpy_h2d(engine.handle, slot, self.d_sched, tab.ctypes.data, tab.nbytes))
+        self.d_params = self._upload(params)
+        self.d_sched = self._upload(tab)
+        self.d_coh = self._alloc(8 * N.NCOH * n)
+        self.d_status = self._alloc(4 * n)
 
     def launch(self, timed: bool = False) -> float:
-        ms = ctypes.c_float(0.0)
-        N.check(self.eng.lib.ryd_run_schedule_coherences_device(
+        return self._timed(lambda ms: self.eng.lib.ryd_run_schedule_coherences_device(
             self.eng.handle, self.slot, ctypes.byref(self.desc), self.d_params, self.n, self.n,
-            self.d_sched, self.ld_sched, self.d_coh, self.n, self.d_status, None,
-            ctypes.byref(ms) if timed else None))
-        return float(ms.value)
-
-    def mark(self, which: int):
-        N.check(self.eng.lib.ryd_mark(self.eng.handle, self.slot, which))
-
-    def mark_elapsed(self) -> float:
-        ms = ctypes.c_float(0.0)
-        N.check(self.eng.lib.ryd_mark_elapsed(self.eng.handle, self.slot, ctypes.byref(ms)))
-        return float(ms.value)
-
-    def synchronize(self):
-        N.check(self.eng.lib.ryd_synchronize(self.eng.handle))
+            self.d_sched, self.ld_sched, self.d_coh, self.n, self.d_status, None, ms), timed)
 
     def fetch(self) -> Tuple[np.ndarray, np.ndarray]:
-        lib, h, s = self.eng.lib, self.eng.handle, self.slot
-        coh = np.zeros((N.NCOH, self.n))
-        status = np.zeros(self.n, dtype=np.uint32)
-        N.check(lib.ryd_memcpy_d2h(h, s, coh.ctypes.data, self.d_coh, coh.nbytes))
-        N.check(lib.ryd_memcpy_d2h(h, s, status.ctypes.data, self.d_status, status.nbytes))
-        return coh, status
-
-    def free(self):
-        for p in self._bufs:
-            self.eng.lib.ryd_free(self.eng.handle, self.slot, p)
-        self._bufs = []
+        return self._fetch_coherences()

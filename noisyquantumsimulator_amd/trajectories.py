@@ -26,7 +26,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from .engine import Engine, default_n_steps
+from .engine import Engine, _DeviceBuffers, default_n_steps
 
 DIM = 27
 LABELS3 = tuple(f"{a}{b}{c}" for a in "01" for b in "01" for c in "01")
@@ -189,7 +189,7 @@ def run_trajectories(engine: Engine, params: np.ndarray, protocol: str, psi0: Op
                             st.kernel_ms, st.h2d_ms, st.d2h_ms)
 
 
-class TrajectoryDeviceBatch:
+class TrajectoryDeviceBatch(_DeviceBuffers):
     """Inputs resident in HBM on one device slot, for timed re-runs (bench.py) and
     shards launched with their global point indices: point i of the batch is global point
     ``point_offset + point_stride * i`` (a range shard: stride 1; rank r of a strided split
@@ -202,8 +202,8 @@ class TrajectoryDeviceBatch:
                  point_offset: int = 0, records: bool = False, kernel: str = "auto", point_stride: int = 1):
         if point_stride < 1 or point_offset < 0:
             raise ValueError("point_stride must be >= 1 and point_offset >= 0")
-        self.eng, self.slot, self.point_offset = engine, slot, point_offset
-        lib = engine.lib
+        super().__init__(engine, slot)
+        self.point_offset = point_offset
         params = np.ascontiguousarray(params, dtype=np.float64)
         self.n = n = params.shape[1]
         if n_steps is None:
@@ -212,56 +212,25 @@ class TrajectoryDeviceBatch:
         self.desc = make_traj_desc(protocol, plus_state() if psi0 is None else psi0, n_traj, seed,
                                    ladder_levels, n_steps, shape, kernel)
         self.desc.point_stride = point_stride
-        self._bufs = []
-
-        def alloc(nbytes):
-            p = ctypes.c_void_p()
-            N.check(lib.ryd_malloc(engine.handle, slot, nbytes, ctypes.byref(p)))
-            self._bufs.append(p)
-            return p
-        self.d_params = alloc(params.nbytes)
-        self.d_rho = alloc(8 * N.T["RHO_WIDTH"] * n)
-        self.d_se = alloc(8 * N.T["SE_WIDTH"] * n)
-        self.d_summary = alloc(8 * N.T_NSUMMARY * n)
-        self.d_status = alloc(4 * n)
-        self.d_rec = alloc(8 * N.T["REC_WIDTH"] * n_traj * n) if records else None
-        N.check(lib.ryd_memcpy_h2d(engine.handle, slot, self.d_params, params.ctypes.data, params.nbytes))
+        self.d_params = self._upload(params)
+        self.d_rho = self._alloc(8 * N.T["RHO_WIDTH"] * n)
+        self.d_se = self._alloc(8 * N.T["SE_WIDTH"] * n)
+        self.d_summary = self._alloc(8 * N.T_NSUMMARY * n)
+        self.d_status = self._alloc(4 * n)
+        self.d_rec = self._alloc(8 * N.T["REC_WIDTH"] * n_traj * n) if records else None
 
     def launch(self, timed: bool = False) -> float:
-        ms = ctypes.c_float(0.0)
-        N.check(self.eng.lib.ryd_run_trajectories_device(
+        return self._timed(lambda ms: self.eng.lib.ryd_run_trajectories_device(
             self.eng.handle, self.slot, ctypes.byref(self.desc), self.d_params, self.n, self.n,
             self.point_offset, self.d_rho, N.T["RHO_WIDTH"], self.d_se, N.T["SE_WIDTH"], self.d_summary,
-            self.n, self.d_rec, self.d_status, None, ctypes.byref(ms) if timed else None))
-        return float(ms.value)
-
-    def mark(self, which: int):
-        """Record HIP event `which` (0 = region start, 1 = region end) on the launch stream."""
-        N.check(self.eng.lib.ryd_mark(self.eng.handle, self.slot, which))
-
-    def mark_elapsed(self) -> float:
-        ms = ctypes.c_float(0.0)
-        N.check(self.eng.lib.ryd_mark_elapsed(self.eng.handle, self.slot, ctypes.byref(ms)))
-        return float(ms.value)
-
-    def synchronize(self):
-        N.check(self.eng.lib.ryd_synchronize(self.eng.handle))
+            self.n, self.d_rec, self.d_status, None, ms), timed)
 
     def fetch(self) -> TrajectoryResult:
-        lib, h, s = self.eng.lib, self.eng.handle, self.slot
-        rho = np.zeros((self.n, N.T["RHO_WIDTH"]))
-        se = np.zeros((self.n, N.T["SE_WIDTH"]))
-        summ = np.zeros((N.T_NSUMMARY, self.n))
-        status = np.zeros(self.n, dtype=np.uint32)
-        for arr, d in ((rho, self.d_rho), (se, self.d_se), (summ, self.d_summary), (status, self.d_status)):
-            N.check(lib.ryd_memcpy_d2h(h, s, arr.ctypes.data, d, arr.nbytes))
+        rho = self._download(np.zeros((self.n, N.T["RHO_WIDTH"])), self.d_rho)
+        se = self._download(np.zeros((self.n, N.T["SE_WIDTH"])), self.d_se)
+        summ = self._download(np.zeros((N.T_NSUMMARY, self.n)), self.d_summary)
+        status = self._download(np.zeros(self.n, dtype=np.uint32), self.d_status)
         rec = None
         if self.d_rec is not None:
-            rec = np.zeros((self.n, self.n_traj, N.T["REC_WIDTH"]))
-            N.check(lib.ryd_memcpy_d2h(h, s, rec.ctypes.data, self.d_rec, rec.nbytes))
+            rec = self._download(np.zeros((self.n, self.n_traj, N.T["REC_WIDTH"])), self.d_rec)
         return TrajectoryResult(self.n, self.n_traj, unpack_rho(rho), unpack_se(se), summ, status, rec)
-
-    def free(self):
-        for p in self._bufs:
-            self.eng.lib.ryd_free(self.eng.handle, self.slot, p)
-        self._bufs = []

@@ -124,6 +124,19 @@ def _chunk_batch(ns: int) -> Dict:
     return dict(params=p, sched=s)
 
 
+NAN_ROW = 2
+
+
+def nan_last_segment(name: str = "chunk17"):
+    """Batch ``name`` with a NaN in the last segment of point NAN_ROW's table -- the segment that
+    the lanes past n_seg of a partial last chunk read too -- between untouched neighbours:
+    (params, sched, good), ``good`` the other points, whose oracle rows are the batch's own."""
+    b = batch(name)
+    s = b["sched"].copy()
+    s[NAN_ROW, N.SC["DELTA"], -1] = np.nan
+    return b["params"], s, [i for i in range(s.shape[0]) if i != NAN_ROW]
+
+
 NAMES = ("random", "lp_square", "bangbang", "smooth_jp") + tuple(f"chunk{ns}" for ns in CHUNK_NSEG)
 
 

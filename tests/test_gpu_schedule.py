@@ -184,6 +184,20 @@ def test_refused_rows(eng, shapes, kind):
             np.testing.assert_array_equal(r.state[:, 4 * i:4 * i + 4], inputs, err_msg=f"{kind}: row {i}")
 
 
+def test_nan_in_the_last_segment(eng):
+    """n_seg = 17: the NaN sits alone in the partial second chunk, where every lane past it reads
+    it again.  Its row is refused; the neighbours are the oracle's, as in test_chunk_edges."""
+    p, s, good = SP.nan_last_segment()
+    r = eng.run_schedule(p, s)
+    np.testing.assert_array_equal(r.status, np.where(np.arange(5) == SP.NAN_ROW, BAD, 0))
+    err = float(np.abs(r.rho()[good] - SP.golden("chunk17")[good]).max())
+    print(f"NaN in the last segment: neighbours max|drho| = {err:.3e}")
+    assert err < TOL
+    inputs = np.zeros((25, 4))
+    inputs[0, 0] = inputs[1, 1] = inputs[5, 2] = inputs[6, 3] = 1.0
+    np.testing.assert_array_equal(r.state[:, 4 * SP.NAN_ROW:4 * SP.NAN_ROW + 4], inputs)
+
+
 # ---- 8. summary-only, device-resident
 def test_summary_only_and_device_batch(eng):
     b = SP.batch("random")

@@ -194,6 +194,18 @@ def test_refused_rows(eng, shapes, kind):
             np.testing.assert_array_equal(coh[:, i], IDENTITY, err_msg=f"{kind}: row {i}")
 
 
+def test_nan_in_the_last_segment(eng):
+    """n_seg = 17: the NaN sits alone in the partial second chunk, where every lane past it reads
+    it again.  Its row is refused; the neighbours are the oracle's, as in test_chunk_edges."""
+    p, s, good = SP.nan_last_segment()
+    coh, st = eng.run_schedule_coherences(p, s)
+    np.testing.assert_array_equal(st, np.where(np.arange(5) == SP.NAN_ROW, BAD, 0))
+    err = float(np.abs(coh[:, good] - _golden_rows("chunk17")[:, good]).max())
+    print(f"NaN in the last segment: neighbours max|d coh| = {err:.3e}")
+    assert err < TOL
+    np.testing.assert_array_equal(coh[:, SP.NAN_ROW], IDENTITY)
+
+
 # ---- 8. step cap
 @pytest.mark.parametrize("row", [0, 2, 4])
 def test_step_cap(eng, row):

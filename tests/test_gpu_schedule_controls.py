@@ -236,6 +236,22 @@ def test_refused_rows(eng, shapes, kind):
             np.testing.assert_array_equal(_bits(r.control_jacobian[i]), 0, err_msg=f"{kind}: Jacobian row {i}")
 
 
+def test_nan_in_the_last_segment(eng):
+    """n_seg = 17: the NaN sits alone in the partial second chunk, where every lane past it reads
+    it again and where the backward walk starts.  Its row is refused; the neighbours are the
+    oracle's, as in test_against_oracle."""
+    p, s, good = SP.nan_last_segment()
+    r = _ctl(eng, p, s)
+    ref = CP.reference("chunk17")
+    np.testing.assert_array_equal(r.status, np.where(np.arange(5) == SP.NAN_ROW, BAD, 0))
+    kerr = float(np.abs(r.kets()[good] - ref["kets"][good]).max())
+    errs = _field_errors(r.control_jacobian[good], ref["C"][good])
+    print(f"NaN in the last segment: neighbours max|dpsi| = {kerr:.3e}, " +
+          ", ".join(f"max|dJ_{f}| = {errs[f]:.3e}" for f in FIELDS))
+    assert kerr < TOL and max(errs.values()) < TOL
+    np.testing.assert_array_equal(_bits(r.control_jacobian[SP.NAN_ROW]), 0)
+
+
 def test_step_cap(eng, shapes):
     p0, s0, _ = shapes
     p, s = p0[:, :8].copy(), s0[:8].copy()

@@ -255,6 +255,24 @@ def test_refused_rows(eng, shapes, kind):
             np.testing.assert_array_equal(_bits(r.phase_jacobian[i]), 0, err_msg=f"{kind}: Jacobian row {i}")
 
 
+def test_nan_in_the_last_segment(eng):
+    """n_seg = 17: the NaN sits alone in the partial second chunk, where every lane past it reads
+    it again and where the backward walk starts.  Its row is refused; the neighbours are the
+    oracle's, as in test_against_oracle."""
+    p, s, good = SP.nan_last_segment()
+    r = eng.run_schedule_kets(p, s, jacobian=True)
+    ref = KP.reference("chunk17")
+    np.testing.assert_array_equal(r.status, np.where(np.arange(5) == SP.NAN_ROW, BAD, 0))
+    err = float(np.abs(r.kets()[good] - ref["kets"][good]).max())
+    jerr = float(np.abs(r.phase_jacobian[good] - ref["J"][good]).max())
+    print(f"NaN in the last segment: neighbours max|dpsi| = {err:.3e}, max|dJ| = {jerr:.3e}")
+    assert max(err, jerr) < TOL
+    basis = np.zeros((4, 9), complex)
+    basis[0, 0] = basis[1, 1] = basis[2, 3] = basis[3, 4] = 1.0
+    np.testing.assert_array_equal(_bits(r.kets()[SP.NAN_ROW]), _bits(basis))
+    np.testing.assert_array_equal(_bits(r.phase_jacobian[SP.NAN_ROW]), 0)
+
+
 def test_step_cap(eng, shapes):
     p0, s0, _ = shapes
     p, s = p0[:, :8].copy(), s0[:8].copy()

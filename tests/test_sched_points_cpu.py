@@ -29,6 +29,17 @@ def test_batches_are_what_the_issue_asks():
         assert SP.golden(name).shape == (p.shape[1], 4, 9, 9)
 
 
+def test_nan_last_segment_leaves_the_neighbours_alone():
+    """The refused point's neighbours keep their tables, so the recorded chain of chunk17 (one
+    full chunk and a one-segment partial one; finite, checked below with every batch) is theirs."""
+    b = SP.batch("chunk17")
+    p, s, good = SP.nan_last_segment()
+    assert p is b["params"] and s.shape == (5, 4, 17) and good == [0, 1, 3, 4]
+    np.testing.assert_array_equal(s[good], b["sched"][good])
+    assert np.isnan(s[SP.NAN_ROW, :, -1]).sum() == 1 and np.all(np.isfinite(s[SP.NAN_ROW, :, :-1]))
+    assert np.all(np.isfinite(b["sched"])) and np.all(np.isfinite(SP.golden("chunk17")[good]))
+
+
 @pytest.mark.slow
 @pytest.mark.parametrize("name", SP.NAMES)
 def test_oracle_chain(name):
