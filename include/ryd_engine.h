@@ -333,7 +333,10 @@ int ryd_destroy(ryd_handle* h);
 /* Host buffers in/out; range-partitions the points over the handle's devices
  * (one stream each, no inter-device communication), blocks until done.
  * out_state may be NULL (summary-only, see the data layout above): the device workspace,
- * the pinned staging, the D2H and the unpack then carry the summary and status alone. */
+ * the pinned staging, the D2H and the unpack then carry the summary and status alone.
+ * A RYD_STATUS_BAD_INPUT point (Omega <= 0, tau <= 0, a negative rate, or a non-finite Omega, V,
+ * Delta, delta1, tau or rate) sets that bit alone, its state rows hold the untouched inputs
+ * (rho_x = |x><x|, or the basis kets) and the other points of the batch do not depend on it. */
 int ryd_run_batch(ryd_handle* h, const ryd_batch_desc* desc,
                   const double* params, int64_t n, int64_t ld_params,
                   double* out_state, int64_t ld_state,

@@ -112,6 +112,36 @@ __device__ __forceinline__ void sh_step(double& b, double t, double a, const dou
   else if constexpr (SH_CHAINS == 2) b += b1;
 }
 
+// The point a row computes with: its own when valid, else a neutral one (unit Rabi frequency,
+// xi = 1, everything else 0).  An invalid row is inactive (sc = 0) but its generator rows, its
+// bound and its amplitudes are still formed, and 0 * inf or 0 * NaN from a non-finite column
+// would reach its state through the identity steps; with finite constants the row keeps its
+// inputs exactly.  A valid row's values pass through unchanged, and each selected value is
+// opaque to the compiler, as a loaded one is: the arithmetic that follows is then formed (and
+// contracted into FMAs) as it is without the selection, so a valid row keeps its bits.
+__device__ __forceinline__ double sh_pick(bool valid, double x, double neutral) {
+  double r = valid ? x : neutral;
+  asm volatile("" : "+v"(r));
+  return r;
+}
+__device__ __forceinline__ PointP sh_point_or_neutral(const PointP& q, bool valid) {
+  PointP r = q;
+  r.Om = sh_pick(valid, q.Om, 1.0);
+  r.Dl = sh_pick(valid, q.Dl, 0.0);
+  r.V = sh_pick(valid, q.V, 0.0);
+  r.d1 = sh_pick(valid, q.d1, 0.0);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    r.gA[c] = sh_pick(valid, q.gA[c], 0.0);
+    r.gB[c] = sh_pick(valid, q.gB[c], 0.0);
+  }
+  r.tau = sh_pick(valid, q.tau, 0.0);
+  r.xr = sh_pick(valid, q.xr, 1.0);
+  r.xi = sh_pick(valid, q.xi, 0.0);
+  r.corr = sh_pick(valid, q.corr, 1.0);
+  return r;
+}
+
 template <int PROTO>
 __global__ __launch_bounds__(SH_BLOCK) __attribute__((amdgpu_waves_per_eu(RYD_SH16_OCC, 8))) void
 lindblad_shaped16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st,
@@ -128,8 +158,9 @@ lindblad_shaped16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp,
   const int64_t gi = xcd_block(blockIdx.x, gridDim.x) * SH_PPW + row;
   const bool live = gi < n;
   const int64_t i = live ? gi : n - 1;
-  const PointP q0 = load_point<PROTO>(prm, ldp, i);
-  const bool valid = live && point_valid<PROTO>(q0, n_steps);
+  const PointP qin = load_point<PROTO>(prm, ldp, i);
+  const bool valid = live && point_valid<PROTO>(qin, n_steps);
+  const PointP q0 = sh_point_or_neutral(qin, valid);
   double* Lc = s_buf[row];
   double* Mc = s_buf[row] + NS * 16;
   double* stg = s_buf[row];
