@@ -68,6 +68,15 @@ struct ryd_handle {
   std::mutex mu;                  // one host-buffer call at a time per handle
 };
 
+// The launch of the CU-balanced sym16 LP-square kernels (ryd_sym16.inc).  They are compiled in
+// a translation unit of their own, ryd_sym16_bal.hip, whose compiler option preloads their
+// first arguments into SGPRs (an option of the whole unit: every other kernel keeps its code).
+// form: 2 the one-instruction parameter load, 1 the 64-bit column loads; state: false takes the
+// summary-only twin.  cfg = s16_bal_cfg(gpc, st32, nohandoff, wt).
+__attribute__((visibility("hidden"))) hipError_t ryd_s16_bal_launch(
+    int form, bool state, unsigned workgroups, unsigned block, hipStream_t stream, const double* prm, int64_t n,
+    int64_t ldp, int cfg, double* sm, uint32_t* status, int64_t ldm, double* st, int64_t lds, int n_steps);
+
 namespace {
 
 constexpr int BLOCK = 256;
@@ -1798,6 +1807,11 @@ __global__ __launch_bounds__(BLOCK, OCC) void jp_frame_kernel(
 #define RYD_LP_UNSQUARED 2                   // LP square, identical atoms: squaring levels left to the states
 #endif
 #include "ryd_sym16.inc"
+#ifdef RYD_S16_BAL_TU
+// ryd_sym16_bal.hip, the balanced sym16 kernels' own translation unit, takes this file up to
+// here: the device code those kernels are made of, and nothing that would emit another kernel
+}  // namespace
+#else
 // custom pulse schedules on the same row layout: the table reader, then ryd_run_schedule
 #include "ryd_sched_table.inc"
 #include "ryd_sched16.inc"
@@ -2566,13 +2580,11 @@ int launch_sym16(const double* dp, int64_t n, int64_t ldp, double* ds, int64_t l
       // 0 .. RYD_P_XI_IM = 14
       static_assert(RYD_P_XI_IM == 14, "the largest LP-square parameter column");
       const bool p32 = sym16_param32_enabled() && ldp <= (0x7fffffffLL / 8 - n) / 14;
-      auto fb = p32 ? lindblad_sym16_kernel<RYD_PROTO_LP_SQUARE, 2> : lindblad_sym16_kernel<RYD_PROTO_LP_SQUARE, 1>;
-      if (!ds)
-        fb = p32 ? lindblad_sym16_nostate_kernel<RYD_PROTO_LP_SQUARE, 2>
-                 : lindblad_sym16_nostate_kernel<RYD_PROTO_LP_SQUARE, 1>;
       const int noh = eh && eh[0] == '1', wt = wtm >= 0 ? wtm : S16_WT_AUTO;
-      return launch_typed(fb, pl.workgroups, S16_BLOCK * pl.waves, 0, stream, dp, n, ldp, ds, lds, dm, ldm, dstat,
-                          ns, pl.gpc, st32, noh, wt);
+      if (pl.workgroups > 0x7fffffffLL) return fail(RYD_ERR_INVALID, "batch too large for one launch");
+      HIPCHK(ryd_s16_bal_launch(p32 ? 2 : 1, ds != nullptr, (unsigned)pl.workgroups, S16_BLOCK * pl.waves, stream, dp,
+                                n, ldp, s16_bal_cfg(pl.gpc, st32, noh, wt), dm, dstat, ldm, ds, lds, ns));
+      return RYD_OK;
     }
   }
   // the one-wave kernels have plain stores only: a forced write-through cannot be honoured
@@ -3732,3 +3744,4 @@ int ryd_derive(ryd_handle* h, const ryd_derive_desc* desc, const double* in, int
 }
 
 }  // extern "C"
+#endif  // RYD_S16_BAL_TU

@@ -176,6 +176,47 @@ __device__ __forceinline__ void dot5_bcast(double& acc, double x, double o0, dou
 // are cleared by LDS reads of a zero word instead of VALU moves: 10 VALU fewer per
 // squaring, the reads land while the m < 5 groups run.
 typedef const __attribute__((address_space(3))) double lds_zero_t;
+
+// MASK (RYD_S16_MASK_IDLE, the balanced form's first build): the 150 FMAs of the m >= 5 groups
+// with lanes 0-4 and 15 of every row switched off.  There own = U[m][c] is a structural zero
+// (c < 5 <= m; lane 15's column is all zeros), so the unmasked form adds +-0 to accumulators
+// that started from +0 and are never -0: the same bits for finite columns.  The broadcast
+// sources are lanes 5-14, which stay on (a DPP read of a lane that exec switches off is
+// invalid), and a row is on or off as a whole under the caller's `if (it < sq)`.  One asm
+// statement, so that no compiler-made move can fall under the narrowed exec; exec is ANDed, not
+// overwritten, and restored.  An SALU write of exec needs no wait states before a VALU op; the
+// s_nop covers a source copied just before the statement (VALU write -> DPP read).
+#ifndef RYD_S16_MASK_IDLE
+#define RYD_S16_MASK_IDLE 1                  // C2 -0.19 to -0.21 us, in-kernel clock 1.98 -> 2.00 GHz: profiles/sym16_entry/
+#endif
+#define S16_SQ_F(k, kc, m, mc) \
+  "v_fmac_f64_dpp %" #k ", %" #kc ", %" #mc " row_newbcast:" #m " row_mask:0xf bank_mask:0xf\n\t"
+#define S16_SQ_G(m, mc)                                                                                    \
+  S16_SQ_F(0, 16, m, mc) S16_SQ_F(1, 17, m, mc) S16_SQ_F(2, 18, m, mc) S16_SQ_F(3, 19, m, mc)              \
+  S16_SQ_F(4, 20, m, mc) S16_SQ_F(5, 21, m, mc) S16_SQ_F(6, 22, m, mc) S16_SQ_F(7, 23, m, mc)              \
+  S16_SQ_F(8, 24, m, mc) S16_SQ_F(9, 25, m, mc) S16_SQ_F(10, 26, m, mc) S16_SQ_F(11, 27, m, mc)            \
+  S16_SQ_F(12, 28, m, mc) S16_SQ_F(13, 29, m, mc) S16_SQ_F(14, 30, m, mc)
+__device__ __forceinline__ void square_upper_masked(const double (&c)[NS], double (&a)[NS]) {
+  static_assert(NS == 15, "operands 0-14: accumulators, 15: the saved exec, 16-30: columns");
+  uint64_t saved;
+  asm volatile(
+      "s_mov_b64 %15, exec\n\t"
+      "s_and_b32 exec_lo, exec_lo, 0x7fe07fe0\n\t"
+      "s_and_b32 exec_hi, exec_hi, 0x7fe07fe0\n\t"
+      "s_nop 1\n\t"
+      S16_SQ_G(5, 21) S16_SQ_G(6, 22) S16_SQ_G(7, 23) S16_SQ_G(8, 24) S16_SQ_G(9, 25)
+      S16_SQ_G(10, 26) S16_SQ_G(11, 27) S16_SQ_G(12, 28) S16_SQ_G(13, 29) S16_SQ_G(14, 30)
+      "s_mov_b64 exec, %15"
+      : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]), "+v"(a[8]),
+        "+v"(a[9]), "+v"(a[10]), "+v"(a[11]), "+v"(a[12]), "+v"(a[13]), "+v"(a[14]), "=&s"(saved)
+      : "v"(c[0]), "v"(c[1]), "v"(c[2]), "v"(c[3]), "v"(c[4]), "v"(c[5]), "v"(c[6]), "v"(c[7]), "v"(c[8]), "v"(c[9]),
+        "v"(c[10]), "v"(c[11]), "v"(c[12]), "v"(c[13]), "v"(c[14])
+      : "scc");
+}
+#undef S16_SQ_G
+#undef S16_SQ_F
+
+template <bool MASK = false>
 __device__ __forceinline__ void square_cols16(const double (&col)[NS], double (&acc)[NS], lds_zero_t* zl) {
   asm volatile("" ::: "memory");             // the zero words are re-read, not forwarded
 #pragma unroll
@@ -185,7 +226,7 @@ __device__ __forceinline__ void square_cols16(const double (&col)[NS], double (&
     acc[k] = zl[k - 5];                      // keeps the loads single (a merged b128 pair
     asm volatile("" ::: "memory");           // would need adjacent registers: v_mov copies)
   }
-  static_for<NS>([&](auto M) {
+  static_for<MASK ? 5 : NS>([&](auto M) {
     constexpr int m = decltype(M)::value;
     const double own = col[m];               // U[m][c]
     // U[k][m] = 0 for k >= 5 > m: the lower-left block is structurally zero
@@ -204,6 +245,7 @@ __device__ __forceinline__ void square_cols16(const double (&col)[NS], double (&
                             col[14], own);
     }
   });
+  if constexpr (MASK) square_upper_masked(col, acc);
 }
 
 // ---- laser phases (smooth JP, bang-bang) -------------------------------------------
@@ -798,9 +840,9 @@ __device__ __forceinline__ bool build16(double (&u)[NS], double (&Ut)[S16_PPW][N
     for (int it = it0; it < it1; it += 2) {
       double w[NS];                          // ping-pong: v -> w -> v (nothing carried in w)
       if (RYD_S16_PRIO_SPLIT && it == ((smx >> 1) & ~1)) s16_phase_prio<1>(ho);   // second half of the squarings
-      if (it < sq) square_cols16(v, w, zl);
+      if (it < sq) square_cols16<SPLIT && RYD_S16_MASK_IDLE != 0>(v, w, zl);
       if (it + 1 < sq) {
-        square_cols16(w, v, zl);
+        square_cols16<SPLIT && RYD_S16_MASK_IDLE != 0>(w, v, zl);
       } else if (it < sq) {
 #pragma unroll
         for (int k = 0; k < NS; ++k) v[k] = w[k];
@@ -1052,7 +1094,7 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
                       int n_steps, int shape, int st32) {
   (void)shape;
   constexpr int BAL = PROTO < 0 ? 1 : 0;     // 0, and dependent: the balanced form's statements are discarded
-  constexpr int gpc = 0, nohandoff = 0, wt = 0, p32 = 0;
+  constexpr int gpc = 0, nohandoff = 0, wt = 0, p32 = 0, nwg = 0;
   constexpr bool STATE = true;
 #include "ryd_sym16_body.inc"
 }
@@ -1066,7 +1108,7 @@ lindblad_sym16_nostate_kernel(const double* __restrict__ prm, int64_t n, int64_t
                               int n_steps, int shape, int st32) {
   (void)shape;
   constexpr int BAL = PROTO < 0 ? 1 : 0;
-  constexpr int gpc = 0, nohandoff = 0, wt = 0, p32 = 0;
+  constexpr int gpc = 0, nohandoff = 0, wt = 0, p32 = 0, nwg = 0;
   constexpr bool STATE = false;
 #include "ryd_sym16_body.inc"
 }
@@ -1078,13 +1120,26 @@ lindblad_sym16_nostate_kernel(const double* __restrict__ prm, int64_t n, int64_t
 // picks it where the offsets fit).  A template argument, not a kernel argument: behind a
 // run-time branch the compiler merges the two forms' loads and gives every column a per-lane
 // 64-bit address.
+// The argument list is the launch's entry: the first eight arguments, 14 dwords -- what a wave
+// needs up to its parameter load, then what the summary stores need -- are the ones the
+// balanced kernels' translation unit (ryd_sym16_bal.hip) has preloaded into SGPRs, so no wave
+// waits for an argument fetch before its load.  `cfg` packs the small integers (s16_bal_cfg),
+// `nwg` is the grid size (gridDim.x would be a fetch from the implicit arguments).
+__host__ __device__ constexpr int s16_bal_cfg(int gpc, int st32, int nohandoff, int wt) {
+  return gpc | (st32 ? 32 : 0) | (nohandoff ? 64 : 0) | (wt << 7);
+}
+#define RYD_S16_BAL_PARAMS                                                                                   \
+  const double* __restrict__ prm, int64_t n, int64_t ldp, int cfg, int nwg, double* __restrict__ sm,         \
+      uint32_t* __restrict__ status, int64_t ldm, double* __restrict__ st, int64_t lds, int n_steps
+#define RYD_S16_BAL_UNPACK                                                                                   \
+  static_assert(PROTO == RYD_PROTO_LP_SQUARE && (BAL == 1 || BAL == 2), "the balanced form is built for LP square"); \
+  static_assert(S16_BAL_MAXW < 32, "gpc takes cfg's low five bits");                                         \
+  constexpr int p32 = BAL == 2;                                                                              \
+  const int gpc = cfg & 31, st32 = cfg & 32, nohandoff = cfg & 64, wt = cfg >> 7
 template <int PROTO, int BAL>
 __global__ __launch_bounds__(S16_BLOCK * S16_BAL_MAXW) __attribute__((amdgpu_waves_per_eu(RYD_S16_WAVES, 8))) void
-lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st,
-                      int64_t lds, double* __restrict__ sm, int64_t ldm, uint32_t* __restrict__ status,
-                      int n_steps, int gpc, int st32, int nohandoff, int wt) {
-  static_assert(PROTO == RYD_PROTO_LP_SQUARE && (BAL == 1 || BAL == 2), "the balanced form is built for LP square");
-  constexpr int p32 = BAL == 2;
+lindblad_sym16_kernel(RYD_S16_BAL_PARAMS) {
+  RYD_S16_BAL_UNPACK;
   constexpr bool STATE = true;
 #include "ryd_sym16_body.inc"
 }
@@ -1092,11 +1147,8 @@ lindblad_sym16_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, do
 // the balanced form's summary-only twin (`wt & S16_WT_SUMMARY` still selects write-through)
 template <int PROTO, int BAL>
 __global__ __launch_bounds__(S16_BLOCK * S16_BAL_MAXW) __attribute__((amdgpu_waves_per_eu(RYD_S16_WAVES, 8))) void
-lindblad_sym16_nostate_kernel(const double* __restrict__ prm, int64_t n, int64_t ldp, double* __restrict__ st,
-                              int64_t lds, double* __restrict__ sm, int64_t ldm, uint32_t* __restrict__ status,
-                              int n_steps, int gpc, int st32, int nohandoff, int wt) {
-  static_assert(PROTO == RYD_PROTO_LP_SQUARE && (BAL == 1 || BAL == 2), "the balanced form is built for LP square");
-  constexpr int p32 = BAL == 2;
+lindblad_sym16_nostate_kernel(RYD_S16_BAL_PARAMS) {
+  RYD_S16_BAL_UNPACK;
   constexpr bool STATE = false;
 #include "ryd_sym16_body.inc"
 }

@@ -16,7 +16,7 @@
   s16_ts[8] = (double)__builtin_amdgcn_s_memrealtime();
   S16_MARK(0);
   s16_ts[10] = s16_ts[11] = 0.0;             // balanced form: role and handoff record
-  s16_ts[12] = 0.0;                          // balanced form: the barrier's stamp
+  s16_ts[12] = 0.0;                          // balanced form: roles known, the consumer's flag cleared
   int bal_polls = 0;
 #endif
   __shared__ double ZlW[NW][16];             // zero words: squaring accumulator clears, lane 15's row
@@ -34,14 +34,15 @@
   int64_t job = 0;
   if constexpr (BAL != 0) {
     role = s16_bal_role(gpc, wv);
-    job = s16_bal_job(blockIdx.x, gridDim.x, role.off);
-    // the flags start clear in every launch (LDS keeps what the last workgroup left): the
-    // one workgroup barrier of the kernel, before the roles part ways.  (Requesting the
-    // parameter columns before it, with every kernel argument fetched at entry, shortens the
-    // start-up by 0.05 us and lengthens the launch by 0.4 us: the barrier waits for the
-    // workgroup's last-dispatched wave, not for memory -- profiles/sym16_edges/.)
-    if (threadIdx.x < 2) Hflag[threadIdx.x] = 0;
-    __syncthreads();
+    job = s16_bal_job(blockIdx.x, nwg, role.off);
+    // No workgroup barrier.  LDS keeps what the last workgroup left, so a consumer clears its
+    // own flag before its first poll (same wave, same address: ordered) and the producer only
+    // sets it.  A consumer then acts only on a flag this workgroup's producer set after the
+    // clear; in every other interleaving (the producer's store came first and was cleared) it
+    // exhausts its polls and runs the producer's part itself -- the same bits.  The barrier
+    // this replaces waited for the workgroup's last-dispatched wave (profiles/sym16_entry/).
+    if (role.role == S16_BAL_CONSUMER)
+      __hip_atomic_store(&Hflag[role.off - (gpc & ~3)], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     S16_MARK(12);
     // a job past the batch: its producer and its consumer both leave here, by the same test
     if (job >= (n + S16_PPW - 1) / S16_PPW) return;

@@ -30,22 +30,43 @@ def tool(name, *args):
     return subprocess.run([os.path.join(LLVM, name), *args], check=True, capture_output=True, text=True).stdout
 
 
-def code_object(path, tmp, tag):
-    """path -> a gfx950 ELF: out of the host library's fat binary, out of a bundle, or as given."""
+BUNDLE = b"__CLANG_OFFLOAD_BUNDLE__"
+
+
+def code_objects(path, tmp, tag):
+    """path -> its gfx950 ELFs: out of the host library's fat binary (one bundle per translation
+    unit that holds kernels), out of a bundle, or the file as given."""
     with open(path, "rb") as f:
         magic = f.read(24)
     if magic.startswith(b"\x7fELF") and magic[18:20] != b"\xe0\x00":      # host ELF (not EM_AMDGPU)
         fat = os.path.join(tmp, tag + ".fatbin")
-        tool("llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, path)
-        path, magic = fat, b"__CLANG_OFFLOAD_BUNDLE__"
-    if magic.startswith(b"__CLANG_OFFLOAD_BUNDLE__"):
-        target = next(t for t in tool("clang-offload-bundler", "--list", "--type=o", "--input=" + path).split()
+        # (with an output file of its own: without one llvm-objcopy rewrites its input in place)
+        tool("llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, path, os.path.join(tmp, tag + ".copy"))
+        path, magic = fat, BUNDLE
+    if not magic.startswith(BUNDLE):
+        return [path]
+    with open(path, "rb") as f:
+        data = f.read()
+    out, at = [], data.find(BUNDLE)
+    while at >= 0:                                                         # the section is the bundles in a row
+        nxt = data.find(BUNDLE, at + 1)
+        one = os.path.join(tmp, f"{tag}{len(out)}.bundle")
+        with open(one, "wb") as f:
+            f.write(data[at:nxt if nxt >= 0 else len(data)])
+        target = next(t for t in tool("clang-offload-bundler", "--list", "--type=o", "--input=" + one).split()
                       if t.endswith("gfx950"))
-        co = os.path.join(tmp, tag + ".co")
-        tool("clang-offload-bundler", "--unbundle", "--type=o", "--targets=" + target, "--input=" + path,
-             "--output=" + co)
-        path = co
-    return path
+        out.append(os.path.join(tmp, f"{tag}{len(out)}.co"))
+        tool("clang-offload-bundler", "--unbundle", "--type=o", "--targets=" + target, "--input=" + one,
+             "--output=" + out[-1])
+        at = nxt
+    return out
+
+
+def merged(dicts):
+    out = {}
+    for d in dicts:
+        out.update(d)
+    return out
 
 
 def kernels(co):
@@ -101,8 +122,9 @@ def main():
     ap.add_argument("--all", action="store_true", help="list the kernels with identical disassembly too")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
-        cos = [code_object(p, tmp, t) for p, t in ((a.base, "base"), (a.new, "new"))]
-        (kb, kn), (fb, fn) = [kernels(c) for c in cos], [functions(c) for c in cos]
+        cos = [code_objects(p, tmp, t) for p, t in ((a.base, "base"), (a.new, "new"))]
+        kb, kn = [merged(kernels(c) for c in cs) for cs in cos]
+        fb, fn = [merged(functions(c) for c in cs) for cs in cos]
     bad = False
     for only, where in ((set(kb) - set(kn), "base"), (set(kn) - set(kb), "new")):
         for s in sorted(only):

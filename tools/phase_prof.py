@@ -7,7 +7,7 @@ the PROF build also records each wave's role and polls and the producer's stamps
 then adds the cycles per role, the distribution of wave end times, the consumers that polled
 more than once or fell back, and per workgroup the SIMD every role ran on.
 For both forms the 'load' phase is split at the PROF build's start-up stamps (the workgroup
-barrier passed, the parameter column loads issued, their values in hand), and the waves' span
+roles known and the consumer's flag cleared, the parameter column loads issued, their values in hand), and the waves' span
 from the first start to the last end is set against the kernel's time: what is left is
 dispatch before the first wave and drain after the last.
 """
@@ -62,8 +62,8 @@ for n in ns:
               f"{np.percentile(x, 90):7.0f}  max {x.max():7.0f}")
     print("  'load' in parts:")
     if np.all(bar > 0) and np.all(bar <= iss):                   # barrier first
-        dist("entry -> barrier passed", bar)
-        dist("barrier passed -> column loads issued", iss - bar)
+        dist("entry -> roles known (no barrier)", bar)
+        dist("roles known -> column loads issued", iss - bar)
         dist("column loads issued -> values in hand", hand - iss)
     elif np.all(bar > 0):                                        # loads first
         dist("entry -> column loads issued", iss)
